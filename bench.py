@@ -9,14 +9,21 @@ N > 1 the default is configs[3] as written -- ONE batch of 1,048,576 headers
 per step cut into N/G contiguous shards (strong scaling; no data-path
 collective) -- and the step ends with the one RCCL all-gather of verdicts and
 VRF outputs the north star names; the weak-scaling figure (1,048,576 headers
-per GPU) is reported beside it as `weak`.  --weak makes weak scaling the line.
+per GPU) is reported beside it as `weak` by --full.  --weak makes weak scaling the line.
 
 Inputs are synthesised on the device (lib/libouro_synth.so, deterministic
 seeds) and are resident in HBM before timing starts.  The
 CPU baseline is the oracle (oracle/build/liboracle.so, a C port) on a bounded
 sample of the same headers, at the box's CPU share of threads.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--headers H]
+A plain run sets up, warms up, times --steps steps and prints the result
+line.  Everything else the benchmark measures -- the measured peak and clock
+of the roofline, the standalone kernels, single items, the host-buffer and
+raw-CBOR legs, the configs[4] latency leg, the CPU baselines -- runs with
+--full.  --dump-outputs DIR writes what the last timed step computed.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--headers H] [--full]
+                  [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -1385,6 +1392,32 @@ def single_item_leg(ed, hdr, iters: int = 300):
     return res
 
 
+DUMP_BETA_ROWS = 65536
+
+
+def dump_outputs(path: str, verdict, beta_eta, beta_leader) -> None:
+    """--dump-outputs: what the timed path returned in its last step, as
+    float32 .npy files (byte values are exact in float32): verdict.npy (n,),
+    and beta_eta.npy / beta_leader.npy (m, 64), the rows beta_rows.npy names
+    -- all n rows up to DUMP_BETA_ROWS, beyond that a fixed seeded sample of
+    DUMP_BETA_ROWS rows in ascending order (36 MB in all at n = 1,048,576).
+    The arguments are (n,), (n*64,), (n*64,) uint8 tensors."""
+    import torch
+
+    n = verdict.shape[0]
+    if n > DUMP_BETA_ROWS:
+        rows = np.sort(np.random.default_rng(20260101).choice(n, DUMP_BETA_ROWS, replace=False))
+    else:
+        rows = np.arange(n)
+    idx = torch.from_numpy(rows).to(verdict.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "verdict.npy"), verdict.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "beta_rows.npy"), rows.astype(np.float64))
+    for name, b in (("beta_eta", beta_eta), ("beta_leader", beta_leader)):
+        a = b.reshape(n, 64)[idx].cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def step_shards(world: int, rank: int, headers: int, global_headers: int, weak: bool):
     """This rank's share of a step: (strong, n, first, n_global).  N = 1: one
     batch of `headers`.  N > 1: configs[3] as written by default -- ONE batch
@@ -1417,6 +1450,17 @@ def main():
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: weak scaling (--headers per GPU) as the line")
     ap.add_argument("--pools", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark "
+                         "measures: the roofline's measured peak, clock and executed work, the "
+                         "standalone kernels, single items, the host-buffer, raw-CBOR, Byron "
+                         "and latency legs, --inproc, the CPU baselines and, at N > 1, the "
+                         "weak-scaling figure and each rank's H2D rate (the --no-* switches "
+                         "trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's results to DIR as "
+                         "float32 .npy: verdict, and the beta_rows rows of beta_eta / "
+                         "beta_leader (see dump_outputs)")
     ap.add_argument("--cpu-sample", type=int, default=65536)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
@@ -1438,6 +1482,12 @@ def main():
                     help="nccl (RCCL over xGMI, the real path) or gloo (rehearsal of the "
                          "multi-rank path on fewer GPUs: ranks share devices, gather via host)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: the timed steps and the result line only
+        args.no_cpu = args.no_extras = args.no_latency = args.no_e2e = True
+        args.inproc = None
 
     import torch
     import torch.distributed as dist
@@ -1472,7 +1522,7 @@ def main():
                                       "host": socket.gethostname()})
         check_rank_devices(topo, args.gpus, allow_shared=args.dist_backend != "nccl")
 
-    from ouroboros_network_amd.shard import all_gather_results, pack_results
+    from ouroboros_network_amd.shard import all_gather_results, pack_results, unpack_results
 
     strong, n, first, n_global = step_shards(world, rank, args.headers, args.global_headers,
                                              args.weak)
@@ -1563,6 +1613,18 @@ def main():
         dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
         all_ok = bool(ok_t.item())
 
+    if args.dump_outputs:
+        # the last timed step's output set is the current one (hdr.use above)
+        if world > 1:
+            if rank == 0:
+                v, be, bl = unpack_results(gather())
+                dump_outputs(args.dump_outputs, *(torch.from_numpy(np.ascontiguousarray(a))
+                                                  for a in (v, be.reshape(-1), bl.reshape(-1))))
+            else:
+                gather()
+        else:
+            dump_outputs(args.dump_outputs, hdr.verdict, hdr.beta_eta, hdr.beta_leader)
+
     total = n_global * args.steps
     value = total / elapsed
     ms_per_step = elapsed / args.steps * 1e3
@@ -1570,17 +1632,19 @@ def main():
     if world > 1:
         # what the process group itself reports, and every rank's kernel time
         per_rank = [None] * world
-        try:
-            bw = h2d_gbps(device)
-        except Exception:  # noqa: BLE001
-            bw = None
+        bw = None
+        if args.full:
+            try:
+                bw = h2d_gbps(device)
+            except Exception:  # noqa: BLE001
+                pass
         dist.all_gather_object(per_rank, {"rank": rank, "device": gpu, "headers": n,
                                           "bus_id": pci_bus_id(device),
                                           "kernel_ms": round(kern_ms, 3),
                                           "numa_node": numa_node, "h2d_gb_per_s": bw})
         dist_info = {"world_size_seen": dist.get_world_size(), "backend": dist.get_backend(),
                      "per_rank": per_rank}
-        if strong:
+        if strong and args.full:
             # the weak-scaling figure beside the strong line: each rank
             # re-verifies its N/G shard G times per step (1,048,576 headers of
             # kernel work per GPU per step when G divides it), then gathers
@@ -1606,17 +1670,18 @@ def main():
 
     if rank == 0:
         peak = None
-        try:
-            peak = measure_peak_mac(device)
-        except Exception as e:  # noqa: BLE001
-            print(f"# peak microbench failed: {e}", file=sys.stderr)
+        if args.full:
+            try:
+                peak = measure_peak_mac(device)
+            except Exception as e:  # noqa: BLE001
+                print(f"# peak microbench failed: {e}", file=sys.stderr)
         achieved = n * MACS_PER_HEADER / (kern_ms * 1e-3) / 1e12
         traffic_per_header, traffic_meta = load_pmc_traffic()
         # box-independent companions of frac: the clock
         # the header kernel itself ran at on this box (diagnostic stamp
         # build), the INT32 issue ceiling at that clock, the MADs the code
         # executes, and the committed SQ / traffic counters per header
-        clk, clk_how = None, "not measured (--no-extras: the profiling runs)"
+        clk, clk_how = None, "not measured (needs --full without --no-extras)"
         if not args.no_extras:
             try:
                 clk, clk_how = kernel_clock_ghz(hdr, stream)
@@ -1624,7 +1689,7 @@ def main():
                 clk, clk_how = None, f"clock probe failed: {e}"
         cus = torch.cuda.get_device_properties(device).multi_processor_count
         ceiling = cus * 64 * clk * 1e9 / 1e12 if clk else None
-        work = executed_work_per_header()
+        work = executed_work_per_header() if args.full else None
         exec_mads = work["executed_mads_per_header"] if work else None
         roof = {
             "bound": "valu",
