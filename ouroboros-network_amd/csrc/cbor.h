@@ -1,6 +1,6 @@
 // cbor.h -- the TPraos header slicer's parse, shared
 // by the host slicer (csrc/pack.cpp, ouro_tpraos_pack_cbor) and the device one
-// (kernels.hip k_tpraos_pack, ouro_tpraos_pack_cbor_device): one header per
+// (kernels.hip k_tpraos_pack, api_batch.cpp ouro_tpraos_pack_cbor_device): one header per
 // call, no allocation, no recursion (containers are tracked on a bounded
 // stack), byte loops instead of libc, so the same code compiles for gfx950.
 // Acceptance mirrors header.py parse_header / pack item for item

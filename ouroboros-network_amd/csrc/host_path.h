@@ -1,6 +1,6 @@
 // host_path.h -- the product's host (CPU) path: the same lane routines the
 // kernels run (verify.h, tpraos.h, leader.h), compiled for x86 in
-// host_path.hip and called by the runtime in kernels.hip.
+// host_path.hip and called by the runtime's host units (api_batch.cpp, raw_pipe.cpp, plan.cpp).
 //
 // Two uses (VERDICT r03 "next" item 4; SURVEY.md §5 and §8(b) "Errors"):
 //   * single items.  The reference calls the crypto one header at a time

@@ -51,7 +51,6 @@ void load(Knobs& k) {
   read_int(k.plan_graph, "OURO_PLAN_GRAPH", 0);
   read_int(k.plan_trim, "OURO_PLAN_TRIM", 1);
   read_int(k.plan_flag, "OURO_PLAN_FLAG", 1);
-  read_int(k.plan_launcher, "OURO_PLAN_LAUNCHER", 1);
   k.plan_timing.store(getenv("OURO_PLAN_TIMING") != nullptr, std::memory_order_relaxed);
   read_int(k.split, "OURO_SPLIT", 0);
   read_int(k.lat_skip, "OURO_LAT_SKIP", 0);

@@ -9,7 +9,8 @@
 //
 // Every field is an atomic so a reload racing a call is well defined (the
 // call sees either value).  Defaults are the product's; the A/B-only
-// switches are documented where they are used (kernels.hip).
+// switches are documented where they are used (runtime.cpp's accessors,
+// plan.cpp plan_build, raw_pipe.cpp).
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -42,7 +43,6 @@ struct Knobs {
   std::atomic<int> plan_graph{0};            // OURO_PLAN_GRAPH
   std::atomic<int> plan_trim{1};             // OURO_PLAN_TRIM
   std::atomic<int> plan_flag{1};             // OURO_PLAN_FLAG
-  std::atomic<int> plan_launcher{1};         // OURO_PLAN_LAUNCHER (0: launches on the caller)
   std::atomic<int> plan_timing{0};           // OURO_PLAN_TIMING (timing probe)
   // honoured by the test-hook build only (-DOURO_TEST_HOOKS=1)
   std::atomic<int> split{0};                 // OURO_SPLIT (the split kernels, rejected)

@@ -1,0 +1,87 @@
+// launches.h -- what the kernel unit (kernels.hip) offers the host runtime:
+// one launch function per kernel or kernel sequence.  The host units reach the
+// kernels only through these; no host unit holds a kernel or a launch
+// (tests/test_abi.py::test_no_getenv_on_call_paths).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/ouro_verify.h"
+#include "cbor.h"
+#include "cbor_byron.h"
+
+// the byte ranges of a plan window's copy kernel (kernels.hip
+// k_plan_stage_ranges), filled by ouro_tpraos_plan_submit (plan.cpp)
+constexpr int kPlanMaxRanges = 24;
+struct PlanRanges {
+  uint32_t count;
+  uint32_t start16[kPlanMaxRanges];
+  uint32_t len16[kPlanMaxRanges];
+};
+
+int lat_fused_items_host();  // kernels_lat.hip: waves per header of the fused launch
+int lat_stamps_read(unsigned long long* out);  // kernels_lat.hip: the latency probe's stamps
+
+#pragma GCC visibility push(hidden)
+namespace ouro_rt {
+
+struct DeviceState;  // runtime.h
+
+enum KernelId { kEd = 0, kVrf = 1, kKes = 2, kHdr = 3, kP2H = 4, kCores = 5, kFinish = 6,
+                kLeader = 7, kHdrPre = 8, kHdrDsm = 9, kHdrPost = 10, kEdPre = 11, kKesPre = 12,
+                kNumKernels = 13 };
+const void* kernel_ptr(int id);
+
+// byron = 1: ByronDSIGN acceptance (cardano-crypto)
+int launch_ed(hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
+              const uint64_t* off, const uint32_t* len, uint8_t* verdict, uint32_t byron = 0);
+int launch_vrf(hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* proof,
+               const uint8_t* alpha, const uint64_t* off, const uint32_t* len, uint8_t* beta,
+               uint8_t* verdict, uint32_t flags = 0);
+int launch_kes(hipStream_t st, size_t n, const uint8_t* vk, const uint32_t* t, const uint8_t* msg,
+               const uint64_t* off, const uint32_t* len, const uint8_t* sig, uint8_t* verdict);
+int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b, uint8_t* verdict, uint8_t* be,
+               uint8_t* bl);
+int launch_leader(hipStream_t st, size_t n, const uint8_t* beta, const uint64_t* num,
+                  const uint64_t* den, int64_t lhi, uint64_t llo, int f_is_one,
+                  uint8_t* verdict);
+
+// latency mode: eight cores per header (x4 lanes in quad mode), then the
+// finish; n and the option bits read from d_n[0..1].
+// Lanes used <= the kBlock-rounded count lowlat_scratch_words provides for.
+// The launch shape (grids, option bits: the OURO_LAT_* switches) is fixed per
+// capacity; a plan computes it once at build (lat_shape) and issues it per
+// window (lat_issue) when it launches without a graph.
+struct LatShape {
+  int g1 = 0, g2 = 0, blk = 0, quad = 0, wide_lanes = 0;
+  bool fused = false;
+  uint32_t flags = 0;
+  const int32_t* btab = nullptr;
+};
+
+int lat_shape(size_t n_cap, LatShape* s);
+// (win_ctr / done: a plan's window counter and done word, or null)
+void lat_issue(hipStream_t st, const LatShape& s, const ouro_tpraos_batch& b, const uint32_t* d_n,
+               int32_t* res_buf, int32_t* scratch, uint8_t* verdict, uint8_t* be, uint8_t* bl,
+               uint32_t* win_ctr = nullptr, uint32_t* done = nullptr);
+int launch_lowlat(hipStream_t st, const ouro_tpraos_batch& b, const uint32_t* d_n, size_t n_cap,
+                  int32_t* res_buf, int32_t* scratch, uint8_t* verdict, uint8_t* be,
+                  uint8_t* bl);
+size_t lowlat_scratch_words(DeviceState* ds, size_t n_cap);
+
+// the kernels the runtime launches itself (grid of `blocks` workgroups; the
+// caller checks the launch, runtime.h launch_check)
+void launch_tpraos_pack(hipStream_t st, unsigned blocks, const uint8_t* raw, size_t raw_bytes,
+                        const uint64_t* off, const uint32_t* len, size_t n, uint64_t spkp,
+                        const ouro::cbor::Out& o, uint8_t* status);
+void launch_byron_pack(hipStream_t st, unsigned blocks, const uint8_t* raw, size_t raw_bytes,
+                       const uint64_t* off, const uint32_t* len, size_t n, int64_t magic,
+                       const ouro::cbor::ByronOut& o, uint8_t* status);
+void launch_vrf03_proof_to_hash(hipStream_t st, unsigned blocks, size_t n, const uint8_t* proof,
+                                uint8_t* beta, uint8_t* verdict);
+void launch_plan_stage(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst, size_t n16,
+                       uint64_t* stamp);
+void launch_plan_stage_ranges(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst,
+                              const PlanRanges& r, uint64_t* stamp);
+
+}  // namespace ouro_rt
+#pragma GCC visibility pop

@@ -3,7 +3,7 @@
 // (NUMA-local)").
 //
 // A device's NUMA node is the `numa_node` file of its PCI function in sysfs
-// (the PCI bus id comes from hipDeviceGetPCIBusId in kernels.hip); the node's
+// (the PCI bus id comes from hipDeviceGetPCIBusId in runtime.cpp); the node's
 // CPUs are its `cpulist`.  Binding a thread = restricting its affinity to
 // those CPUs (intersected with what the process may use: a container's
 // cpuset is honoured, and an empty intersection leaves the thread alone) and

@@ -1,0 +1,494 @@
+// raw_pipe.cpp -- raw header CBOR in host memory -> verdicts in one call: the
+// chunked multi-slot pipeline (raw_run), its host-path recompute, and the
+// *_verify_cbor entries.  Host code only: kernels are reached through
+// launches.h.
+// its own host copies of the out-of-line lane routines (common.h)
+#define OURO_NI_LINKAGE static
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/ouro_verify.h"
+#include "cbor.h"
+#include "cbor_byron.h"
+#include "host_path.h"
+#include "knobs.h"
+#include "launch.h"
+#include "launches.h"
+#include "runtime.h"
+#include "task_pool.h"
+
+using namespace ouro;
+using namespace ouro_rt;
+
+// ---- raw header CBOR in host memory -> verdicts in one call -----------------
+// The reference's bulk callers hold raw header bytes in host memory: ChainDB's
+// re-validation of a chain suffix (ouroboros-consensus/src/Ouroboros/Consensus/
+// Storage/ChainDB/Impl/LgrDB.hs:350-368), ChainSync windows
+// (.../MiniProtocol/ChainSync/Client.hs:792), and storage integrity on every
+// block (.../Storage/VolatileDB/Impl/Parser.hs:66-85,
+// .../Storage/ImmutableDB/Impl/Validation.hs:358-365).  raw_run takes such a
+// batch straight through the device:
+//   * the batch is cut into chunks of whole headers (OURO_CBOR_CHUNK headers,
+//     default 65,536, and at most kRawChunkBytes of raw bytes each);
+//   * chunk c runs on slot c % S (S = OURO_CBOR_SLOTS streams, default 6 for
+//     headers, 4 for integrity):
+//     the library's worker pool gathers its header spans from the caller's
+//     pageable buffer into the slot's pinned, NUMA-local staging (runs of
+//     adjacent spans as one memcpy; offsets rebased by a prefix sum), the
+//     slot's stream uploads that block -- the raw bytes, ~1 KB per header,
+//     not the 1.4 KB SoA --, runs the device slicer (k_tpraos_pack) into the
+//     slot's arena, then the header kernel with mkSeed from (slot, eta0) on
+//     the device (or the Sum6KES kernel, for integrity), and copies status,
+//     verdicts and outputs back into pinned memory;
+//   * before reusing a slot the host harvests its previous chunk into the
+//     caller's buffers, so up to S chunks are in flight: the host's gathers,
+//     the uploads and the other slots' kernels overlap, and the kernels of
+//     neighbouring chunks share the CUs as each one's waves retire.
+// A device error stops the pipeline (everything in flight is waited for) and
+// the whole batch is recomputed on the host path (raw_host).
+namespace {
+constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
+constexpr size_t kRawChunkBytes = (size_t)96 << 20;
+
+// (RawKind, RawCall: runtime.h)
+struct RawChunk {
+  size_t lo, m, bytes;
+};
+
+// the pinned / device input block of a chunk of m headers and `bytes` raw bytes
+struct RawIn {
+  size_t off, len, eta0, alpha, raw, total;
+};
+RawIn raw_in(size_t m, size_t bytes, bool alphas) {
+  RawIn l;
+  l.off = 0;
+  l.len = a16(8 * m);
+  l.eta0 = l.len + a16(4 * m);
+  l.alpha = l.eta0 + 32;
+  l.raw = a16(l.alpha + (alphas ? 64 * m : 0));
+  l.total = l.raw + a16(std::max<size_t>(bytes, 16));
+  return l;
+}
+// its result block: status | verdict | beta_eta | beta_leader | eta_nonce | slot
+struct RawOut {
+  size_t status, verdict, be, bl, nonce, slot, total;
+};
+RawOut raw_out(size_t m) {
+  RawOut o;
+  o.status = 0;
+  o.verdict = a16(m);
+  o.be = o.verdict + a16(m);
+  o.bl = o.be + 64 * m;
+  o.nonce = o.bl + 64 * m;
+  o.slot = o.nonce + 32 * m;  // device only: the slicer's slots for mkSeed
+  o.total = o.slot + 8 * m;
+  return o;
+}
+// bytes of the result block copied back
+size_t raw_out_bytes(const RawCall& c, const RawOut& o, size_t m) {
+  if (c.kind != kRawHdr) return o.verdict + m;
+  if (c.nonce) return o.slot;
+  if (c.bl) return o.nonce;
+  if (c.be) return o.bl;
+  return o.verdict + m;
+}
+
+// Every span inside raw (as ouro_tpraos_pack_cbor demands), and the chunks.
+// a raw-CBOR knob (knobs.h; 0 = unset) if inside [lo, hi], else the default
+size_t knob_size(const std::atomic<size_t>& k, size_t dflt, size_t lo, size_t hi) {
+  const size_t v = k.load(std::memory_order_relaxed);
+  return v && v >= lo && v <= hi ? v : dflt;
+}
+
+// Headers in chunk j when `left` headers (this chunk's included) remain.
+// ramp (OURO_CBOR_RAMP=1, A/B): the first chunks a quarter and a half of
+// `per`, so the first kernel starts after a short gather and upload, and the
+// last ones halving down to a quarter, so the chip is not left running one
+// full chunk's kernel alone at the end.  It lost: 77.5 -> 85.3 ms per 1M
+// headers (profiles/r05o/cbor_ramp_ab.jsonl) -- a small chunk's kernel runs
+// at a fraction of the chip with nothing beside it; off by default.
+size_t raw_chunk_target(size_t j, size_t left, size_t per, bool ramp) {
+  if (!ramp) return per;
+  size_t t = j == 0 ? per / 4 : (j == 1 ? per / 2 : per);
+  if (left <= per + per / 2) t = std::min(t, std::max(per / 4, left / 2));
+  return std::max<size_t>(t, 256);
+}
+
+int raw_chunks(const RawCall& c, size_t per, std::vector<RawChunk>* out) {
+  out->clear();
+  const bool ramp = ouro_knobs::get().cbor_ramp.load(std::memory_order_relaxed) == 1;
+  RawChunk k{0, 0, 0};
+  size_t target = raw_chunk_target(0, c.n, per, ramp);
+  for (size_t i = 0; i < c.n; i++) {
+    if (c.off[i] > c.raw_bytes || c.raw_bytes - c.off[i] < c.len[i])
+      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
+    if (k.m && (k.m >= target || k.bytes + c.len[i] > kRawChunkBytes)) {
+      out->push_back(k);
+      k = RawChunk{i, 0, 0};
+      target = raw_chunk_target(out->size(), c.n - i, per, ramp);
+    }
+    k.m++;
+    k.bytes += c.len[i];
+  }
+  if (k.m) out->push_back(k);
+  return OURO_OK;
+}
+
+
+// last call's phases on this thread (ouro_debug_cbor_stats)
+thread_local double t_raw_stats[6] = {-1, -1, -1, -1, -1, -1};
+
+int pinned_at_least(uint8_t** p, size_t* cap, size_t bytes) {
+  if (*cap >= bytes) return OURO_OK;
+  if (*p) OURO_HIP(hipHostFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  // (hipHostMallocNumaUser: the calling thread's NUMA policy -- a bench rank
+  // or multi-device worker is bound to its GPU's node, numa.cpp)
+  OURO_HIP(hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocNumaUser));
+  *cap = bytes;
+  return OURO_OK;
+}
+
+// the chunk's header spans from the caller's buffer into the slot's pinned block
+int raw_stage(RawSlot& s, const RawCall& c, const RawChunk& k, int width) {
+  const bool alphas = c.ea != nullptr;
+  const RawIn L = raw_in(k.m, k.bytes, alphas);
+  int rc = pinned_at_least(&s.h_in, &s.h_in_cap, L.total + L.total / 8);
+  if (rc) return rc;
+  uint64_t* noff = reinterpret_cast<uint64_t*>(s.h_in + L.off);
+  uint64_t at = 0;
+  for (size_t i = 0; i < k.m; i++) {
+    noff[i] = at;
+    at += c.len[k.lo + i];
+  }
+  memcpy(s.h_in + L.len, c.len + k.lo, 4 * k.m);
+  if (c.eta0) memcpy(s.h_in + L.eta0, c.eta0, 32);
+  if (alphas) {
+    memcpy(s.h_in + L.alpha, c.ea + 32 * k.lo, 32 * k.m);
+    memcpy(s.h_in + L.alpha + 32 * k.m, c.la + 32 * k.lo, 32 * k.m);
+  }
+  uint8_t* dst = s.h_in + L.raw;
+  // tasks of ~1 MB: enough to balance, few enough to keep each memcpy long
+  const size_t ntasks = std::max<size_t>(1, std::min<size_t>(k.m, k.bytes >> 20));
+  const int r = ouro_pool::parallel_for(ntasks, width, [&](size_t t) {
+    const size_t a = k.m * t / ntasks, b = k.m * (t + 1) / ntasks;
+    for (size_t i = a; i < b;) {
+      // a run of headers adjacent in the caller's buffer: one memcpy
+      const uint64_t src = c.off[k.lo + i];
+      uint64_t bytes = c.len[k.lo + i];
+      size_t j = i + 1;
+      while (j < b && c.off[k.lo + j] == src + bytes) bytes += c.len[k.lo + j++];
+      memcpy(dst + noff[i], c.raw + src, bytes);
+      i = j;
+    }
+  });
+  return r ? fail(OURO_EDEVICE, "raw CBOR gather failed") : OURO_OK;
+}
+
+// the slot's stream: upload, device slicer, kernel, results back
+int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
+  const bool alphas = c.ea != nullptr;
+  const RawIn L = raw_in(k.m, k.bytes, alphas);
+  const RawOut O = raw_out(k.m);
+  const size_t back = raw_out_bytes(c, O, k.m);
+  int rc;
+  if ((rc = ensure(s.d_in, L.total)) || (rc = ensure(s.d_arena, ouro_tpraos_pack_bytes(k.m))) ||
+      (rc = ensure(s.d_out, O.total)) || (rc = pinned_at_least(&s.h_out, &s.h_out_cap, back)))
+    return rc;
+  uint8_t* din = static_cast<uint8_t*>(s.d_in.p);
+  uint8_t* dout = static_cast<uint8_t*>(s.d_out.p);
+  OURO_HIP(hipMemcpyAsync(din, s.h_in, L.total, hipMemcpyHostToDevice, s.st));
+  const size_t blocks = std::min<size_t>((k.m + kBlock - 1) / kBlock, 4096);
+  if (c.kind == kRawByron) {
+    // the device Byron slicer into the slot's arena, then the Ed25519 kernel
+    // with ByronDSIGN acceptance (cardano-crypto: SURVEY.md App. B.5)
+    const cbor::ByronLayout bl = cbor::byron_layout(k.m, k.bytes + cbor::kByronMsgExtra * k.m);
+    if ((rc = ensure(s.d_arena, bl.total + 64))) return rc;
+    const cbor::ByronOut o = cbor::byron_arena_out(cbor::arena_base(s.d_arena.p), bl);
+    launch_byron_pack(s.st, (unsigned)blocks, din + L.raw, k.bytes,
+                      reinterpret_cast<const uint64_t*>(din + L.off),
+                      reinterpret_cast<const uint32_t*>(din + L.len), k.m, c.magic, o,
+                      dout + O.status);
+    if ((rc = launch_check())) return rc;
+    if ((rc = launch_ed(s.st, k.m, o.pk, o.sig, o.msg, o.msg_off, o.msg_len, dout + O.verdict, 1)))
+      return rc;
+    OURO_HIP(hipMemcpyAsync(s.h_out, dout, back, hipMemcpyDeviceToHost, s.st));
+    OURO_HIP(hipEventRecord(s.done, s.st));
+    s.lo = k.lo;
+    s.m = k.m;
+    s.busy = true;
+    return OURO_OK;
+  }
+  uint64_t* dslot = reinterpret_cast<uint64_t*>(dout + O.slot);
+  const bool seeds = c.kind == kRawHdr && !alphas;
+  const cbor::Out o = cbor::arena_out(cbor::arena_base(s.d_arena.p), k.m, seeds ? dslot : nullptr,
+                                      nullptr);
+  const uint8_t* draw = din + L.raw;
+  launch_tpraos_pack(s.st, (unsigned)blocks, draw, k.bytes,
+                     reinterpret_cast<const uint64_t*>(din + L.off),
+                     reinterpret_cast<const uint32_t*>(din + L.len), k.m, c.spkp, o,
+                     dout + O.status);
+  if ((rc = launch_check())) return rc;
+  ouro_tpraos_batch b{};
+  cbor::batch_from(&b, o, draw, k.m);
+  if (c.kind == kRawKes) {
+    rc = launch_kes(s.st, k.m, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig,
+                    dout + O.verdict);
+  } else {
+    if (alphas) {
+      b.eta_alpha = din + L.alpha;
+      b.leader_alpha = din + L.alpha + 32 * k.m;
+    } else {
+      b.slot = dslot;
+      b.epoch_nonce = c.eta0 ? din + L.eta0 : nullptr;
+    }
+    if (c.nonce) b.eta_nonce = dout + O.nonce;
+    rc = launch_hdr(s.st, b, dout + O.verdict, dout + O.be, dout + O.bl);
+  }
+  if (rc) return rc;
+  OURO_HIP(hipMemcpyAsync(s.h_out, dout, back, hipMemcpyDeviceToHost, s.st));
+  OURO_HIP(hipEventRecord(s.done, s.st));
+  s.lo = k.lo;
+  s.m = k.m;
+  s.busy = true;
+  return OURO_OK;
+}
+
+// the slot's finished chunk into the caller's buffers
+int raw_drain(RawSlot& s, const RawCall& c) {
+  if (!s.busy) return OURO_OK;
+  s.busy = false;
+  OURO_HIP(hipEventSynchronize(s.done));
+  const RawOut O = raw_out(s.m);
+  const uint8_t* st = s.h_out + O.status;
+  const uint8_t* v = s.h_out + O.verdict;
+  memcpy(c.status + s.lo, st, s.m);
+  if (c.kind == kRawByron) {
+    // PBFT accepts an epoch-boundary header without a signature
+    // (ouroboros-consensus/src/Ouroboros/Consensus/Protocol/PBFT.hs:327-328)
+    for (size_t i = 0; i < s.m; i++)
+      c.verdict[s.lo + i] = st[i] == OURO_PACK_EBB ? 1 : (st[i] == OURO_PACK_OK && v[i] ? 1 : 0);
+    return OURO_OK;
+  }
+  // a header the slicer rejected is invalid (its zeroed row cannot verify;
+  // masked so that no bit at all is set for it)
+  for (size_t i = 0; i < s.m; i++) c.verdict[s.lo + i] = st[i] == OURO_PACK_OK ? v[i] : 0;
+  if (c.kind == kRawHdr) {
+    if (c.be) memcpy(c.be + 64 * s.lo, s.h_out + O.be, 64 * s.m);
+    if (c.bl) memcpy(c.bl + 64 * s.lo, s.h_out + O.bl, 64 * s.m);
+    if (c.nonce) memcpy(c.nonce + 32 * s.lo, s.h_out + O.nonce, 32 * s.m);
+  }
+  return OURO_OK;
+}
+
+int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  double gather_ms = 0, wait_ms = 0;
+  DeviceState* ds;
+  int dev, rc = device_state(&ds);
+  if (rc || (rc = current_device(&dev))) return rc;
+  RawPipe& p = ctx_of(dev).raw;
+  // chunks in flight: the header kernel wants ~3 grids of work queued (6 x
+  // 64 K headers); the Sum6KES kernel is PCIe-bound, 4 suffice
+  // (profiles/r05a/cbor_sweep.jsonl); Byron's Ed25519 runs best with 5
+  // (66.7--67.1 M headers/s against ~61 with 4 and 60--68 with 6, interleaved
+  // on one box: profiles/r06k/byron_ab.jsonl)
+  const int S = (int)knob_size(ouro_knobs::get().cbor_slots, c.kind == kRawHdr ? 6 : (c.kind == kRawByron ? 5 : 4), 1,
+                                kRawMaxSlots);
+  for (int k = 0; k < S; k++) {
+    RawSlot& s = p.s[k];
+    if (!s.st) OURO_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+    if (!s.done) OURO_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  }
+  const int width = (int)knob_size(ouro_knobs::get().cbor_copy_threads, 8, 1, 64);
+  size_t ci = 0;
+  for (; ci < chunks.size() && !rc; ci++) {
+    RawSlot& s = p.s[ci % S];
+    const auto a = clk::now();
+    rc = raw_drain(s, c);
+    const auto b = clk::now();
+    if (!rc) rc = raw_stage(s, c, chunks[ci], width);
+    const auto d = clk::now();
+    if (!rc) rc = raw_launch(s, c, chunks[ci]);
+    wait_ms += std::chrono::duration<double, std::milli>(b - a).count();
+    gather_ms += std::chrono::duration<double, std::milli>(d - b).count();
+  }
+  // the rest in chunk order; after an error, wait for everything in flight
+  for (int k = 0; k < S; k++) {
+    RawSlot& s = p.s[(ci + k) % S];
+    if (rc) {
+      (void)hipStreamSynchronize(s.st);
+      s.busy = false;
+    } else {
+      const auto a = clk::now();
+      rc = raw_drain(s, c);
+      wait_ms += std::chrono::duration<double, std::milli>(clk::now() - a).count();
+    }
+  }
+  const double total = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  const double st[6] = {total, gather_ms, wait_ms, (double)chunks.size(), (double)S, (double)width};
+  memcpy(t_raw_stats, st, sizeof st);
+  return rc;
+}
+
+// the host path over the same batch: host slicer + host verification, in
+// chunks (no batch-sized arena), results straight into the caller's buffers
+int raw_host_byron(const RawCall& c) {
+  const size_t C = 1 << 16;
+  for (size_t lo = 0; lo < c.n; lo += C) {
+    const size_t m = std::min(C, c.n - lo);
+    const size_t nb = ouro_byron_pack_bytes(m, c.len + lo);
+    std::unique_ptr<uint8_t[]> arena(new (std::nothrow) uint8_t[nb]);  // every row written
+    if (!arena) return fail(OURO_EDEVICE, "raw Byron host path: out of host memory");
+    ouro_byron_batch b;
+    int rc = ouro_byron_pack_cbor(c.raw, c.raw_bytes, c.off + lo, c.len + lo, m, c.magic,
+                                  arena.get(), nb, &b, c.status + lo, 0);
+    if (rc) return fail(rc, "ouro_byron_pack_cbor: bad arguments");
+    if ((rc = ouro_host::ed_batch(m, b.pk, b.sig, b.msg, b.msg_off, b.msg_len, c.verdict + lo, 1)))
+      return fail(rc, "raw Byron host path failed");
+    for (size_t i = lo; i < lo + m; i++)
+      c.verdict[i] = c.status[i] == OURO_PACK_EBB ? 1
+                                                  : (c.status[i] == OURO_PACK_OK && c.verdict[i]);
+  }
+  return OURO_OK;
+}
+
+int raw_host(const RawCall& c) {
+  if (c.kind == kRawByron) return raw_host_byron(c);
+  const size_t C = 1 << 16;
+  const size_t cap = std::min(C, c.n);
+  const size_t nb = ouro_tpraos_pack_bytes(cap);
+  std::unique_ptr<uint8_t[]> arena(new (std::nothrow) uint8_t[nb]);
+  std::unique_ptr<uint64_t[]> slots(new (std::nothrow) uint64_t[cap]);
+  if (!arena || !slots) return fail(OURO_EDEVICE, "raw CBOR host path: out of host memory");
+  for (size_t lo = 0; lo < c.n; lo += C) {
+    const size_t m = std::min(C, c.n - lo);
+    ouro_tpraos_batch b{};  // (the slicer sets the required members only)
+    int rc = ouro_tpraos_pack_cbor(c.raw, c.raw_bytes, c.off + lo, c.len + lo, m, c.spkp,
+                                   arena.get(), nb, &b, slots.get(), nullptr, c.status + lo, 0);
+    if (rc) return fail(rc, "ouro_tpraos_pack_cbor: bad arguments");
+    if (c.kind == kRawKes) {
+      rc = ouro_host::kes_batch(m, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig,
+                                c.verdict + lo);
+    } else {
+      if (c.ea) {
+        b.eta_alpha = c.ea + 32 * lo;
+        b.leader_alpha = c.la + 32 * lo;
+      } else {
+        b.slot = slots.get();
+        b.epoch_nonce = c.eta0;
+      }
+      if (c.nonce) b.eta_nonce = c.nonce + 32 * lo;
+      rc = ouro_host::hdr_batch(&b, c.verdict + lo, c.be ? c.be + 64 * lo : nullptr,
+                                c.bl ? c.bl + 64 * lo : nullptr);
+    }
+    if (rc) return fail(rc, "raw CBOR host path failed");
+    for (size_t i = lo; i < lo + m; i++)
+      if (c.status[i] != OURO_PACK_OK) c.verdict[i] = 0;
+  }
+  return OURO_OK;
+}
+}  // namespace
+
+namespace ouro_rt {
+int raw_verify(const RawCall& c) {
+  if (c.n == 0) return OURO_OK;
+  if (!c.raw || !c.off || !c.len || !c.status || !c.verdict)
+    return fail(OURO_EINVAL, "null argument");
+  if (c.kind != kRawByron && c.spkp == 0) return fail(OURO_EINVAL, "zero slots per KES period");
+  if (c.kind == kRawByron && (c.magic < -1 || c.magic > (int64_t)0xffffffffll))
+    return fail(OURO_EINVAL, "protocol magic outside Word32 (or -1)");
+  if ((c.ea == nullptr) != (c.la == nullptr))
+    return fail(OURO_EINVAL, "give both VRF input arrays or neither");
+  std::vector<RawChunk> chunks;
+  const size_t per = knob_size(ouro_knobs::get().cbor_chunk, 65536, 256, (size_t)1 << 24);
+  int rc = raw_chunks(c, per, &chunks);
+  if (rc) return rc;
+  return or_host(raw_run(c, chunks), [&] { return raw_host(c); });
+}
+}  // namespace ouro_rt
+
+extern "C" {
+
+// ---- storage integrity (KES only) over raw headers ----
+// verifyHeaderIntegrity (ouroboros-consensus-shelley/src/Ouroboros/Consensus/
+// Shelley/Ledger/Integrity.hs:20-44): Sum6KES of the raw header body under the
+// opcert's hot key at t = kesPeriod(slot) - c0 (0 below c0) -- the check the
+// VolatileDB parser runs on every block at open
+// (ouroboros-consensus/src/Ouroboros/Consensus/Storage/VolatileDB/Impl/Parser.hs:66-85)
+// and ImmutableDB chunk validation on every block of a chunk
+// (.../ImmutableDB/Impl/Validation.hs:358-365).  The raw-CBOR pipeline above:
+// the device slicer (cbor.h, kes_t_of = Integrity.hs:38-44), then the Sum6KES
+// kernel on its rows; a header the slicer rejects is 0.
+int ouro_integrity_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                               const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
+                               uint8_t* status, uint8_t* verdict) {
+  RawCall c{kRawKes, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, nullptr,
+            nullptr, status, verdict, nullptr, nullptr, nullptr};
+  return raw_verify(c);
+}
+
+// Raw TPraos headers -> the full header check (ouroboros-consensus-shelley/
+// src/Ouroboros/Consensus/Shelley/Protocol.hs:433-442 over each decoded
+// header) in one call through the raw-CBOR pipeline above.
+int ouro_tpraos_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                            const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
+                            const uint8_t* epoch_nonce, const uint8_t* eta_alpha,
+                            const uint8_t* leader_alpha, uint8_t* status, uint8_t* verdict,
+                            uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce) {
+  RawCall c{kRawHdr, raw, raw_bytes, off, len, n, slots_per_kes_period, epoch_nonce, eta_alpha,
+            leader_alpha, status, verdict, beta_eta, beta_leader, eta_nonce};
+  return raw_verify(c);
+}
+
+// Raw Byron headers -> PBFT's block-signature verdicts (ouroboros-consensus/
+// src/Ouroboros/Consensus/Protocol/PBFT.hs:332-338; the storage integrity
+// check ouroboros-consensus-byron/src/Ouroboros/Consensus/Byron/Ledger/
+// Integrity.hs:24-35) through the raw-CBOR pipeline above: chunks gathered
+// into pinned NUMA-local staging, the device Byron slicer (k_byron_pack, the
+// host slicer's cbor_byron.h parse), then the Ed25519 kernel with ByronDSIGN
+// acceptance, five chunks in flight.  An epoch-boundary header is 1 (status
+// OURO_PACK_EBB); a rejected one 0.
+int ouro_byron_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                           const uint32_t* len, size_t n, int64_t protocol_magic,
+                           uint8_t* status, uint8_t* verdict) {
+  RawCall c{kRawByron, raw, raw_bytes, off, len, n, 0, nullptr, nullptr, nullptr, status,
+            verdict, nullptr, nullptr, nullptr, protocol_magic};
+  return raw_verify(c);
+}
+
+// DIAGNOSTIC: the calling thread's last raw-CBOR call (ms and counts)
+int ouro_debug_cbor_stats(double* out6) {
+  if (!out6) return fail(OURO_EINVAL, "null buffer");
+  memcpy(out6, t_raw_stats, sizeof t_raw_stats);
+  return OURO_OK;
+}
+
+// The same on raw headers already in device memory (raw, off, len, arena,
+// status, verdict: device pointers; arena >= ouro_tpraos_pack_bytes(n)):
+// the device slicer and the Sum6KES kernel enqueued on `stream`, not
+// synchronised.  A rejected header's zeroed row (OURO_PACK_*) cannot verify.
+int ouro_integrity_verify_cbor_device(void* stream, const uint8_t* raw, size_t raw_bytes,
+                                      const uint64_t* off, const uint32_t* len, size_t n,
+                                      uint64_t slots_per_kes_period, void* arena,
+                                      size_t arena_bytes, uint8_t* status, uint8_t* verdict) {
+  if (n == 0) return OURO_OK;
+  if (!verdict) return fail(OURO_EINVAL, "null verdict");
+  ouro_tpraos_batch b{};
+  int rc = ouro_tpraos_pack_cbor_device(stream, raw, raw_bytes, off, len, n,
+                                        slots_per_kes_period, arena, arena_bytes, &b, nullptr,
+                                        nullptr, status);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return launch_kes(st, n, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig, verdict);
+}
+
+}  // extern "C"

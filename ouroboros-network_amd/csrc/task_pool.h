@@ -2,7 +2,7 @@
 //
 // Every host-side parallel loop of the product goes through it: the host
 // path's item loops (host_path.hip), the CBOR slicer (pack.cpp) and the
-// gather of raw headers into pinned staging (kernels.hip, the raw-CBOR
+// gather of raw headers into pinned staging (raw_pipe.cpp, the raw-CBOR
 // pipeline).  Threads are started once, on first use, and live until the
 // process exits, so a batch never pays for thread creation and a call
 // behind the C ABI never lets std::system_error or std::bad_alloc escape:

@@ -88,7 +88,7 @@ def test_golden_corruptions_truncations(gpu_lib, kats):
 
 
 def _ramp_chunks(n, per, ramp=True):
-    """chunk count of kernels.hip raw_chunks / raw_chunk_target (the golden
+    """chunk count of raw_pipe.cpp raw_chunks / raw_chunk_target (the golden
     headers are far below the 96 MiB byte cap)"""
     count, j, i = 0, 0, 0
     while i < n:

@@ -134,7 +134,7 @@ def test_nonce_fold_from_device_outputs(gpu_lib, kats):
 
 @contextlib.contextmanager
 def _poisoned_submit():
-    """The plan test hook (kernels.hip plan_poison; the test build only),
+    """The plan test hook (plan.cpp plan_poison; the test build only),
     reached through the environment: every submit while it is set first
     poisons the counters."""
     from ouroboros_network_amd import _native

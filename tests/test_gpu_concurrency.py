@@ -5,7 +5,7 @@ batch calls, every result checked against the oracle -- the header's
 "thread-safe and reentrant" promise, under the reference's one-thread-per-peer
 calling pattern (ouroboros-consensus/src/Ouroboros/Consensus/Network/NodeToNode.hs:173-176)
 -- then 64 short-lived threads one after another, which must reuse one pooled
-context (kernels.hip ThreadCtx / Lease) instead of leaking one each."""
+context (runtime.h ThreadCtx / runtime.cpp Lease) instead of leaking one each."""
 import os
 import subprocess
 

@@ -328,7 +328,7 @@ def test_lowlat_kes_body_lengths(gpu_lib, kats, monkeypatch, form):
 
 def test_pipelined_host_batches(gpu_lib, kats, monkeypatch):
     """Host-buffer header batches larger than one chunk go through the
-    two-stream pipeline (kernels.hip hdr_batch_pipelined): same verdicts and
+    two-stream pipeline (api_batch.cpp hdr_batch_pipelined): same verdicts and
     outputs as one-piece staging and the oracle, for ragged chunk sizes, rows
     in shuffled order (bodies not monotonic in the buffer, with gaps) and an
     empty body in the middle of a chunk."""

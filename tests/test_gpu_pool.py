@@ -1,5 +1,5 @@
-"""Per-thread device contexts are pooled, not leaked (kernels.hip ThreadCtx /
-Lease; include/ouro_verify.h "thread-safe and reentrant").  GHC runs `safe`
+"""Per-thread device contexts are pooled, not leaked (runtime.h ThreadCtx /
+runtime.cpp Lease; include/ouro_verify.h "thread-safe and reentrant").  GHC runs `safe`
 FFI calls on a worker pool that grows and churns, one thread per peer
 (ouroboros-consensus/src/Ouroboros/Consensus/Network/NodeToNode.hs:173-176):
 64 short-lived threads, one after another, each verify a 65,536-header batch
