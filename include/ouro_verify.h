@@ -217,7 +217,25 @@ int ouro_sum6kes_verify_batch(size_t n, const uint8_t *vk /* n x 32 */,
  *   eta_nonce (OUTPUT, n x 32): mkNonceFromOutputVRF of the eta output the
  *     nonce update consumes = Blake2b-256(claimed eta output) when
  *     eta_output is given (the reference's choice), else of the computed
- *     beta_eta.  ouro_nonce_fold folds these into eta_v / eta_c. */
+ *     beta_eta.  ouro_nonce_fold folds these into eta_v / eta_c.
+ *
+ * Shared OCERT checks (deployment knob OURO_OCERT_SHARE, default 1): an
+ * operational certificate is issued once per KES key rotation, so the headers
+ * of a bulk batch carry a handful of distinct ones per pool.  Every GPU header
+ * batch (host buffers, device buffers, raw CBOR) groups its headers by the 144
+ * bytes issuer_vk || hot_vk || ocert_counter || ocert_kes_period ||
+ * ocert_sigma -- equality over all of them, never a hash alone -- and runs the
+ * Ed25519 check once per distinct record; the verdict bits are the ones a
+ * check per header gives (Ed25519 verification is a pure function of key,
+ * message and signature).  The grouping is redone inside every call; nothing
+ * is cached between calls.  A batch of mostly distinct certificates (more
+ * than 7/8 of n) runs the check per header as before.  OURO_OCERT_SHARE=0 in
+ * the environment turns the sharing off.  The latency plans and the host path
+ * never share.
+ * Footprint: the workspace belongs to the calling thread's pooled context, is
+ * kept per stream for its next call and grows with the largest batch seen:
+ * 4 x (the next power of two >= 2n) + 9n bytes, about 17 MB at 1M headers and
+ * 1.1 MB per 65,536-header chunk of the pipelined paths. */
 typedef struct ouro_tpraos_batch {
   size_t n;
   const uint8_t *issuer_vk;        /* n x 32  bheaderVk (cold key)            */

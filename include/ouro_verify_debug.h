@@ -22,7 +22,7 @@ int ouro_debug_host_path(unsigned long long *single_items,
                          unsigned long long *recomputed_batches);
 
 /* Re-read the library's environment switches (OURO_SINGLE_ITEM,
- * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_HOST_*, OURO_CBOR_*,
+ * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_HOST_*, OURO_CBOR_*,
  * OURO_LAT_*, OURO_PLAN_*; csrc/knobs.h).  The library reads them once, on
  * first use, and never on a call path: a process that changes one (tests,
  * bench.py A/B passes) calls this afterwards.  Plans keep the values they
@@ -77,6 +77,13 @@ int ouro_debug_thread_cpus(int *cpus, int max);
  * error) and whose plans honour OURO_TEST_PLAN_POISON; 0 in the product, which
  * reads neither variable. */
 int ouro_debug_test_hooks(void);
+
+/* The distinct operational certificates (144-byte records, see
+ * OURO_OCERT_SHARE in ouro_verify.h) that the calling thread's last header
+ * launch on `stream` found in its batch; 0 when that launch did not share
+ * (OURO_OCERT_SHARE=0).  Synchronises the stream: for tests only.  Negative:
+ * an OURO_E* status. */
+int ouro_debug_last_ocert_groups(void *stream);
 
 /* The calling thread's last raw-CBOR call (ouro_tpraos_verify_cbor /
  * ouro_integrity_verify_cbor): out6 = {total ms, ms gathering header bytes

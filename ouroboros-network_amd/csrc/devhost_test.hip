@@ -264,6 +264,15 @@ void dh_mk_seed(uint8_t* out, int leader, uint64_t slot, const uint8_t* eta0) {
   hdr_seed(a, b, 0, leader != 0, batch_opts(b));
   memcpy(out, a.w, 32);
 }
+// The OCERT sharing key of tpraos.h (kernels.hip k_ocert_group) on a host SoA
+// batch: the hash of header i's 144 key bytes, and whether headers i and j
+// have the same ones.
+unsigned long long dh_ocert_key_hash(const ouro_tpraos_batch* b, size_t i) {
+  return ocert_key_hash(*b, i);
+}
+int dh_ocert_key_equal(const ouro_tpraos_batch* b, size_t i, size_t j) {
+  return ocert_key_equal(*b, i, j) ? 1 : 0;
+}
 // The header drivers of tpraos.h for every header of a host SoA batch.
 // mode 0 = throughput (one lane, key table shared), 1 = latency (a fresh lane
 // per core, no sharing), 2 = latency on lane quads (the four products of each

@@ -160,19 +160,131 @@ __device__ __noinline__ void hdr_finish_item_ni(const ouro_tpraos_batch& b, size
 __device__ unsigned long long g_clock_stamps[kClockSlots][4];
 #endif
 
+// ---- one OCERT verification per distinct certificate (OURO_OCERT_SHARE) -----
+// An operational certificate is issued once per KES key rotation, so the
+// headers of a batch carry a handful of distinct ones per pool, and Ed25519
+// verification is a pure function of (key, message, signature).  Per call
+// (nothing is kept between calls):
+//   k_ocert_group   header i -> rep[i], the first header seen with the same
+//                   144 key bytes (tpraos.h ocert_key_*); the representatives
+//                   listed in uniq[0 .. *ctr);
+//   k_ocert_unique_wide / k_ocert_unique   ocert_ok[uniq[k]] = the check, one
+//                   wave (small counts) or one lane per certificate;
+//   k_tpraos_verify takes ocert_ok[rep[i]] as header i's OCERT flag and runs
+//                   the other five cores.
+// The count stays on the device (no synchronisation, capturable): every
+// kernel reads it and picks its form.  Above kOcertShareMax(n) distinct
+// certificates there is too little to share: the unique kernels return at
+// once and the header kernel runs the OCERT core inline as without sharing,
+// so a batch of distinct certificates costs the group pass and no more.  The
+// threshold is a judgement, not a measurement: at count = n - n/8 the unique
+// pass does 7/8 of the inline work in a kernel of its own, and the 1/8 saved
+// is about what the extra launch and the flag loads cost; the all-distinct
+// A/B only bounds it from above.  OURO_OCERT_BYPASS=0 builds
+// the A/B form that always shares.
+#ifndef OURO_OCERT_BYPASS
+#define OURO_OCERT_BYPASS 1
+#endif
+__host__ __device__ constexpr size_t kOcertShareMax(size_t n) {
+  return OURO_OCERT_BYPASS ? n - n / 8 : n;
+}
+// probes before a header gives up and represents itself (an adversarial batch
+// degrades to the unshared cost, never to a wrong verdict or an unbounded loop)
+constexpr int kOcertProbeCap = 64;
+
+// table: cap_mask + 1 entries, zeroed by the launch (0 = empty, else header
+// index + 1).  Only the CAS's return value is used, never a plain load of the
+// table; the keys compared were written before the launch, so no fence is
+// needed.  hash_mask: all ones (the test build's OURO_TEST_OCERT_HASH_BITS
+// narrows it to exercise probe chains and the cap).
+__global__ void __launch_bounds__(kBlock) k_ocert_group(ouro_tpraos_batch b, uint32_t* table,
+                                                        uint32_t cap_mask, uint32_t hash_mask,
+                                                        uint32_t* __restrict__ rep,
+                                                        uint32_t* __restrict__ uniq,
+                                                        uint32_t* ctr) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  const uint32_t lid = threadIdx.x & 63u;
+  for (size_t base = tid - lid; base < b.n; base += nth) {  // wave-uniform
+    const size_t i = base + lid;
+    bool is_rep = false;
+    if (i < b.n) {
+      uint32_t key[kOcertKeyWords];
+      ocert_key_load(key, b, i);
+      const uint64_t h = ocert_key_hash_words(key);
+      uint32_t slot = (uint32_t)(h ^ (h >> 32)) & hash_mask & cap_mask;
+      uint32_t r = (uint32_t)i;
+      is_rep = true;  // also when the probe cap is reached
+      for (int probe = 0; probe < kOcertProbeCap; probe++) {
+        const uint32_t prev = atomicCAS(&table[slot], 0u, (uint32_t)i + 1u);
+        if (prev == 0u) break;
+        uint32_t other[kOcertKeyWords];
+        ocert_key_load(other, b, prev - 1u);
+        if (ocert_key_equal_words(key, other)) {
+          r = prev - 1u;
+          is_rep = false;
+          break;
+        }
+        slot = (slot + 1u) & cap_mask;
+      }
+      rep[i] = r;
+    }
+    // one add per wave of its representatives' count
+    const unsigned long long m = __ballot(is_rep);
+    if (m) {
+      uint32_t at = 0;
+      if (lid == (uint32_t)__ffsll((long long)m) - 1u) at = atomicAdd(ctr, (uint32_t)__popcll(m));
+      at = __shfl(at, __ffsll((long long)m) - 1);
+      if (is_rep) uniq[at + __popcll(m & ((1ull << lid) - 1ull))] = (uint32_t)i;
+    }
+  }
+}
+
+// The lane form of the unique pass (counts above wide_max, up to share_max):
+// certificate k of uniq[] on one lane, in the header kernel's scratch slots,
+// which are free until the header kernel starts.
+__global__ void __launch_bounds__(kBlock, OURO_WAVES) k_ocert_unique(
+    ouro_tpraos_batch b, const uint32_t* __restrict__ ctr, const uint32_t* __restrict__ uniq,
+    uint8_t* __restrict__ ocert_ok, int32_t* scratch, const int32_t* __restrict__ btab,
+    uint32_t wide_max, uint32_t share_max) {
+  const uint32_t count = *ctr;
+  if (count <= wide_max || count > share_max) return;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  const Slot lane = slot_of(scratch, tid, kSlotWords);
+  for (size_t k = tid; k < count; k += nth) {
+    const size_t i = uniq[k];
+    uint32_t s[16], p[8], hv[8];
+    ld_words(s, b.ocert_sigma + 64 * i, 4);
+    ld_words(p, b.issuer_vk + 32 * i, 2);
+    ld_words(hv, b.hot_vk + 32 * i, 2);
+    OcertMsg m;
+    ocert_msg(m, hv, b.ocert_counter[i], b.ocert_kes_period[i]);
+    ocert_ok[i] = ed25519_verify_lane(s, p, m, 48, lane, btab) ? 1 : 0;
+  }
+}
+
 // Throughput mode: one lane per header runs every core of tpraos.h, sharing
 // the VRF key decode and its table, then the single-inversion finish.
+// rep / ocert_ok / ocert_count (all null when sharing is off): the OCERT
+// verdicts of the unique pass; with at most kOcertShareMax(n) distinct
+// certificates the OCERT core is not run here (a wave-uniform choice).
 __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tpraos_batch b,
                                                              uint8_t* __restrict__ verdict,
                                                              uint8_t* __restrict__ beta_eta,
                                                              uint8_t* __restrict__ beta_leader,
                                                              int32_t* scratch,
-                                                             const int32_t* __restrict__ btab) {
+                                                             const int32_t* __restrict__ btab,
+                                                             const uint32_t* __restrict__ rep,
+                                                             const uint8_t* __restrict__ ocert_ok,
+                                                             const uint32_t* __restrict__ ocert_count) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nth = (size_t)gridDim.x * blockDim.x;
   const Slot lane = slot_of(scratch, tid, kHdrLaneWords);
   const Slot res = lane + kLaneWords;
   const uint32_t opts = batch_opts(b);
+  const bool shared = ocert_count != nullptr && *ocert_count <= kOcertShareMax(b.n);
+  const int core0 = shared ? kCoreKes : kCoreOcert;
 #if OURO_CLOCK_STAMPS
   unsigned long long c0 = 0, r0 = 0;
   if (threadIdx.x == 0) {
@@ -181,12 +293,13 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tprao
   }
 #endif
   for (size_t i = tid; i < b.n; i += nth) {
+    if (shared) stg1(res.word(kResFlags + kCoreOcert), ocert_ok[rep[i]] ? kFlagOk : 0);
 #if OURO_HDR_LOOP
     // one copy of the core dispatch, the core chosen at run time
 #pragma unroll 1
-    for (int c = kCoreOcert; c <= kCoreVl; c++) hdr_core(b, i, opts, c, lane, res, btab);
+    for (int c = core0; c <= kCoreVl; c++) hdr_core(b, i, opts, c, lane, res, btab);
 #else
-    hdr_core(b, i, opts, kCoreOcert, lane, res, btab);
+    if (!shared) hdr_core(b, i, opts, kCoreOcert, lane, res, btab);
     hdr_core(b, i, opts, kCoreKes, lane, res, btab);
     hdr_core(b, i, opts, kCoreUe, lane, res, btab);
     hdr_core(b, i, opts, kCoreUl, lane, res, btab);
@@ -360,6 +473,12 @@ __global__ void k_tpraos_finish(ouro_tpraos_batch b, const uint32_t* __restrict_
                                 int32_t* res_buf, uint8_t* __restrict__ verdict,
                                 uint8_t* __restrict__ beta_eta, uint8_t* __restrict__ beta_leader,
                                 int32_t* scratch, int quad);
+// the wave form of the OCERT unique pass (counts up to wide_max)
+__global__ void k_ocert_unique_wide(ouro_tpraos_batch b, const uint32_t* __restrict__ ctr,
+                                    const uint32_t* __restrict__ uniq,
+                                    uint8_t* __restrict__ ocert_ok,
+                                    const int32_t* __restrict__ btab, uint32_t wide_max,
+                                    uint32_t share_max);
 
 // Raw wire headers -> the SoA on the device, one lane
 // per header: the host slicer's parse (cbor.h, pinned to header.py by
@@ -514,6 +633,7 @@ const void* kernel_ptr(int id) {
     case kHdrPost: return reinterpret_cast<const void*>(&k_hdr_post);
     case kEdPre: return reinterpret_cast<const void*>(&k_ed25519_pre);
     case kKesPre: return reinterpret_cast<const void*>(&k_sum6kes_pre);
+    case kOcertUnique: return reinterpret_cast<const void*>(&k_ocert_unique);
     default: return reinterpret_cast<const void*>(&k_vrf03_proof_to_hash);
   }
 }
@@ -640,11 +760,52 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b, uint8_t* verdict, uin
                          res, verdict, be, bl);
       if ((rc = launch_check())) return rc;
     }
+    ctx().ocert[st].last = nullptr;
     return OURO_OK;
   }
-  if ((rc = plan(ds, kHdr, b.n, st, &grid, &scr, kHdrLaneWords))) return rc;
+  // One OCERT verification per distinct certificate (see k_ocert_group); the
+  // table's entries are header index + 1 and its capacity 2n in 32 bits.
+  OcertWs& ow = ctx().ocert[st];
+  ow.last = nullptr;
+  const uint32_t* rep = nullptr;
+  const uint8_t* ocert_ok = nullptr;
+  const uint32_t* count = nullptr;
+  if (ocert_share() && b.n >= 1 && b.n <= ((size_t)1 << 30)) {
+    size_t cap = 64;
+    while (cap < 2 * b.n) cap <<= 1;
+    // counter (one 16-B row) | table | rep | uniq | ocert_ok
+    const size_t bytes = 16 + 4 * cap + 4 * b.n + 4 * b.n + b.n;
+    if ((rc = ensure(ow.buf, bytes))) return rc;
+    uint32_t* ctr = static_cast<uint32_t*>(ow.buf.p);
+    uint32_t* table = ctr + 4;
+    uint32_t* repw = table + cap;
+    uint32_t* uniq = repw + b.n;
+    uint8_t* okw = reinterpret_cast<uint8_t*>(uniq + b.n);
+    // the unique lane kernel in the header kernel's scratch slots: both plans
+    // before either launch, the pointer taken after the buffer last grew
+    int gu;
+    if ((rc = plan(ds, kOcertUnique, b.n, st, &gu, &scr))) return rc;
+    if ((rc = plan(ds, kHdr, b.n, st, &grid, &scr, kHdrLaneWords))) return rc;
+    OURO_HIP(hipMemsetAsync(ctr, 0, 16 + 4 * cap, st));
+    const size_t gg = (b.n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_ocert_group, dim3((unsigned)gg), dim3(kBlock), 0, st, b, table,
+                       (uint32_t)(cap - 1), ocert_hash_mask(), repw, uniq, ctr);
+    const uint32_t wide_max = (uint32_t)std::min<size_t>(wide_small_max(), 0xffffffffu);
+    const uint32_t share_max = (uint32_t)kOcertShareMax(b.n);
+    if (wide_max)
+      hipLaunchKernelGGL(k_ocert_unique_wide, dim3(wide_grid(std::min<size_t>(b.n, wide_max))),
+                         dim3(64), 0, st, b, ctr, uniq, okw, ds->btab, wide_max, share_max);
+    hipLaunchKernelGGL(k_ocert_unique, dim3(gu), dim3(kBlock), 0, st, b, ctr, uniq, okw, scr,
+                       ds->btab, wide_max, share_max);
+    rep = repw;
+    ocert_ok = okw;
+    count = ctr;
+    ow.last = ctr;
+  } else if ((rc = plan(ds, kHdr, b.n, st, &grid, &scr, kHdrLaneWords))) {
+    return rc;
+  }
   hipLaunchKernelGGL(k_tpraos_verify, dim3(grid), dim3(kBlock), 0, st, b, verdict, be, bl, scr,
-                     ds->btab);
+                     ds->btab, rep, ocert_ok, count);
   return launch_check();
 }
 

@@ -607,6 +607,37 @@ __global__ void __launch_bounds__(64) k_ed25519_wide(size_t n, const uint8_t* __
 #endif
 }
 
+// The wave form of the header batches' OCERT unique pass (kernels.hip
+// k_ocert_group): certificate k of uniq[0 .. *ctr) on one wave -- the OCERT
+// case of hdr_core_wide -- when there are at most wide_max of them (the
+// threshold of the small standalone batches above); the lane form
+// (kernels.hip k_ocert_unique) takes larger counts, and above share_max
+// neither runs.  The count is read here, on the device: the host launches
+// both forms without knowing it.
+__global__ void __launch_bounds__(64) k_ocert_unique_wide(ouro_tpraos_batch b,
+                                                          const uint32_t* __restrict__ ctr,
+                                                          const uint32_t* __restrict__ uniq,
+                                                          uint8_t* __restrict__ ocert_ok,
+                                                          const int32_t* __restrict__ btab,
+                                                          uint32_t wide_max, uint32_t share_max) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t count = *ctr;
+  if (count > wide_max || count > share_max) return;
+  const uint16_t* bw = reinterpret_cast<const uint16_t*>(btab + kBTabWords);
+  for (uint32_t k = blockIdx.x; k < count; k += gridDim.x) {
+    const size_t i = uniq[k];
+    uint32_t s[16], p[8], hv[8];
+    ld_words(s, b.ocert_sigma + 64 * i, 4);
+    ld_words(p, b.issuer_vk + 32 * i, 2);
+    ld_words(hv, b.hot_vk + 32 * i, 2);
+    OcertMsg m;
+    ocert_msg(m, hv, b.ocert_counter[i], b.ocert_kes_period[i]);
+    const bool ok = wide::ed25519_verify_wide(s, p, m, 48, bw);
+    if (threadIdx.x == 0) ocert_ok[i] = ok ? 1 : 0;
+  }
+#endif
+}
+
 __global__ void __launch_bounds__(64) k_vrf03_wide(size_t n, const uint8_t* __restrict__ pk,
                                                    const uint8_t* __restrict__ proof,
                                                    const uint8_t* __restrict__ alpha,

@@ -37,6 +37,7 @@ void load(Knobs& k) {
   read_size<long long>(k.host_chunk, "OURO_HOST_CHUNK", -1);
   read_int(k.host_threads, "OURO_HOST_THREADS", 0);
   k.host_lanes.store(str_is("OURO_HOST_IMPL", "lanes"), std::memory_order_relaxed);
+  read_int(k.ocert_share, "OURO_OCERT_SHARE", 1);
   read_size<size_t>(k.cbor_chunk, "OURO_CBOR_CHUNK", 0);
   read_size<size_t>(k.cbor_slots, "OURO_CBOR_SLOTS", 0);
   read_size<size_t>(k.cbor_copy_threads, "OURO_CBOR_COPY_THREADS", 0);
@@ -59,6 +60,7 @@ void load(Knobs& k) {
   k.test_plan_poison.store(getenv("OURO_TEST_PLAN_POISON") != nullptr, std::memory_order_relaxed);
   k.test_plan_sentinel.store(getenv("OURO_TEST_PLAN_SENTINEL") != nullptr,
                              std::memory_order_relaxed);
+  read_int(k.test_ocert_hash_bits, "OURO_TEST_OCERT_HASH_BITS", 0);
 }
 
 }  // namespace

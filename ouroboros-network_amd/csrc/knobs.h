@@ -26,6 +26,7 @@ struct Knobs {
   std::atomic<long long> host_chunk{-1};     // OURO_HOST_CHUNK (-1: one resident grid)
   std::atomic<int> host_threads{0};          // OURO_HOST_THREADS (0: the default cap)
   std::atomic<int> host_lanes{0};            // OURO_HOST_IMPL=lanes (A/B, bench single_item)
+  std::atomic<int> ocert_share{1};           // OURO_OCERT_SHARE (0: every header's own OCERT check)
   // raw CBOR engine (0: the default; range-checked where used)
   std::atomic<size_t> cbor_chunk{0};         // OURO_CBOR_CHUNK
   std::atomic<size_t> cbor_slots{0};         // OURO_CBOR_SLOTS
@@ -50,6 +51,7 @@ struct Knobs {
   std::atomic<int> test_device_error{0};     // OURO_TEST_DEVICE_ERROR
   std::atomic<int> test_plan_poison{0};      // OURO_TEST_PLAN_POISON
   std::atomic<int> test_plan_sentinel{0};    // OURO_TEST_PLAN_SENTINEL
+  std::atomic<int> test_ocert_hash_bits{0};  // OURO_TEST_OCERT_HASH_BITS (0: the whole hash)
 };
 
 // the switches, loaded from the environment on first use

@@ -28,7 +28,7 @@ struct DeviceState;  // runtime.h
 
 enum KernelId { kEd = 0, kVrf = 1, kKes = 2, kHdr = 3, kP2H = 4, kCores = 5, kFinish = 6,
                 kLeader = 7, kHdrPre = 8, kHdrDsm = 9, kHdrPost = 10, kEdPre = 11, kKesPre = 12,
-                kNumKernels = 13 };
+                kOcertUnique = 13, kNumKernels = 14 };
 const void* kernel_ptr(int id);
 
 // byron = 1: ByronDSIGN acceptance (cardano-crypto)

@@ -215,6 +215,22 @@ bool split_launch() {
   return OURO_SPLIT_DEFAULT != 0;
 }
 
+// Header batches verify each distinct operational certificate once
+// (kernels.hip k_ocert_group; OURO_OCERT_SHARE=0: every header's own check,
+// with no group or unique pass).
+bool ocert_share() { return ouro_knobs::get().ocert_share.load(std::memory_order_relaxed) != 0; }
+
+// The bits of the certificate hash the group pass uses.  The test-hook build
+// narrows them (OURO_TEST_OCERT_HASH_BITS=k) so that a few hundred headers
+// exercise probe chains and the probe cap; the product uses all of them.
+uint32_t ocert_hash_mask() {
+#if OURO_TEST_HOOKS
+  const int k = ouro_knobs::get().test_ocert_hash_bits.load(std::memory_order_relaxed);
+  if (k > 0 && k < 32) return (1u << k) - 1u;
+#endif
+  return 0xffffffffu;
+}
+
 // Workgroup size of the latency-mode launches (OURO_LAT_BLOCK = 64/128/256).
 // A small window fills only a few waves; one-wave workgroups spread them over
 // as many CUs (own L1, TA and instruction fetch per wave) instead of packing
@@ -352,6 +368,23 @@ int ouro_debug_host_path(unsigned long long* single_items, unsigned long long* r
   if (single_items) *single_items = g_host_single.load();
   if (recomputed_batches) *recomputed_batches = g_host_recompute.load();
   return OURO_OK;
+}
+
+// DIAGNOSTIC (tests): the distinct operational certificates the last header
+// launch of the calling thread on `stream` found (runtime.h OcertWs); 0 when
+// that launch did not share.  Synchronises the stream.
+int ouro_debug_last_ocert_groups(void* stream) {
+  int dev;
+  int rc = current_device(&dev);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ThreadCtx& c = ctx_of(dev);
+  auto it = c.ocert.find(st);
+  if (it == c.ocert.end() || !it->second.last) return 0;
+  OURO_HIP(hipStreamSynchronize(st));
+  uint32_t count = 0;
+  OURO_HIP(hipMemcpy(&count, it->second.last, sizeof count, hipMemcpyDeviceToHost));
+  return (int)count;
 }
 
 // Contexts of the per-thread pool on `device` (runtime.h ThreadCtx):

@@ -131,9 +131,20 @@ struct RawPipe {
 // scratch keyed by that stream (work later enqueued on the same stream is
 // ordered after them).  Only the pool itself outlives the process (never
 // freed: the HIP runtime may be gone at teardown).
+// The OCERT sharing workspace of one stream (kernels.hip launch_hdr): the
+// counter, the open-addressing table, rep[n], uniq[n] and ocert_ok[n] --
+// 4 (next power of two >= 2n) + 9n bytes, about 17 MB at 1M headers.
+// last: the device counter of the stream's last header launch (null when that
+// launch did not share), for ouro_debug_last_ocert_groups.
+struct OcertWs {
+  Buf buf;
+  const uint32_t* last = nullptr;
+};
+
 struct ThreadCtx {
   hipStream_t stream = nullptr;
   std::map<hipStream_t, Buf> scratch;  // per stream: concurrent launches never share slots
+  std::map<hipStream_t, OcertWs> ocert;  // per stream, grown like scratch
   Buf in[32];  // staging slots; a header batch uses up to 24
   Pipe pipe;
   RawPipe raw;  // ouro_tpraos_verify_cbor / ouro_integrity_verify_cbor
@@ -174,6 +185,8 @@ int or_host(int rc, F&& recompute) {
 bool single_on_gpu();
 size_t wide_small_max();
 bool split_launch();
+bool ocert_share();
+uint32_t ocert_hash_mask();
 int lat_block();
 int lat_quad();
 int lat_wide_mask();

@@ -436,6 +436,54 @@ OURO_FI void st_words(uint8_t* p, const uint32_t* w, int n16) {
     stg4(p + 16 * i, make_int4((int)w[4 * i], (int)w[4 * i + 1], (int)w[4 * i + 2], (int)w[4 * i + 3]));
 }
 
+// ---- the operational certificate as a key (kernels.hip k_ocert_group) ------
+// A header's OCERT check is a pure function of 144 bytes: issuer_vk[32] ||
+// hot_vk[32] || ocert_counter || ocert_kes_period || ocert_sigma[64].  Headers
+// whose 144 bytes are equal share one verification per batch.  Equality over
+// ALL of the bytes is the correctness condition (a false share would accept a
+// forged certificate); the hash only picks a table slot.
+constexpr int kOcertKeyWords = 36;
+OURO_FI void ocert_key_load(uint32_t w[kOcertKeyWords], const ouro_tpraos_batch& b, size_t i) {
+  ld_words(w, b.issuer_vk + 32 * i, 2);
+  ld_words(w + 8, b.hot_vk + 32 * i, 2);
+  const uint64_t ctr = b.ocert_counter[i], c0 = b.ocert_kes_period[i];
+  w[16] = (uint32_t)ctr;
+  w[17] = (uint32_t)(ctr >> 32);
+  w[18] = (uint32_t)c0;
+  w[19] = (uint32_t)(c0 >> 32);
+  ld_words(w + 20, b.ocert_sigma + 64 * i, 4);
+}
+// any cheap 64-bit mix of the 36 words (multiply-xorshift per word pair)
+OURO_FI uint64_t ocert_key_hash_words(const uint32_t w[kOcertKeyWords]) {
+  uint64_t h = 0x9e3779b97f4a7c15ull;
+#pragma unroll
+  for (int k = 0; k < kOcertKeyWords; k += 2) {
+    h ^= (uint64_t)w[k] | ((uint64_t)w[k + 1] << 32);
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 29;
+  }
+  return h;
+}
+OURO_FI bool ocert_key_equal_words(const uint32_t a[kOcertKeyWords],
+                                   const uint32_t c[kOcertKeyWords]) {
+  uint32_t diff = 0;
+#pragma unroll
+  for (int k = 0; k < kOcertKeyWords; k++) diff |= a[k] ^ c[k];
+  return diff == 0;
+}
+OURO_HD inline uint64_t ocert_key_hash(const ouro_tpraos_batch& b, size_t i) {
+  uint32_t w[kOcertKeyWords];
+  ocert_key_load(w, b, i);
+  return ocert_key_hash_words(w);
+}
+// all 144 bytes of headers i and j, nothing else
+OURO_HD inline bool ocert_key_equal(const ouro_tpraos_batch& b, size_t i, size_t j) {
+  uint32_t a[kOcertKeyWords], c[kOcertKeyWords];
+  ocert_key_load(a, b, i);
+  ocert_key_load(c, b, j);
+  return ocert_key_equal_words(a, c);
+}
+
 // The VRF input of header i: mkSeed seedEta / seedL slot eta0 on the device
 // (Shelley/Protocol.hs:409-410; blake2b.h mkseed_hash) when the batch carries
 // slots, else the caller's 32 bytes.
