@@ -213,7 +213,10 @@ int ouro_sum6kes_verify_batch(size_t n, const uint8_t *vk /* n x 32 */,
  *       seedEta = Blake2b-256(BE64(0)), seedL = Blake2b-256(BE64(1))
  *     (mkNonceFromNumber 0 / 1); epoch_nonce = NULL is NeutralNonce (nothing
  *     appended after the slot).  eta_alpha / leader_alpha are then ignored.
- *     One eta0 per call: a window that crosses an epoch boundary is split.
+ *     These single-nonce members serve ONE epoch: every header of the call
+ *     is seeded with the same eta0.  A batch that crosses an epoch boundary
+ *     goes to ouro_tpraos_verify_batch_epochs (below) with an epoch-nonce
+ *     schedule, a raw stream to ouro_chain_verify_cbor; neither is split.
  *   eta_nonce (OUTPUT, n x 32): mkNonceFromOutputVRF of the eta output the
  *     nonce update consumes = Blake2b-256(claimed eta output) when
  *     eta_output is given (the reference's choice), else of the computed
@@ -265,6 +268,42 @@ typedef struct ouro_tpraos_batch {
  * receive the computed VRF outputs (zeros where a proof fails). */
 int ouro_tpraos_verify_batch(const ouro_tpraos_batch *b, uint8_t *verdict,
                              uint8_t *beta_eta, uint8_t *beta_leader);
+
+/* An epoch-nonce schedule: which eta0 seeds the VRF inputs of which slots, so
+ * that one call verifies a batch spanning several epochs (ChainDB's
+ * re-validation of a stored suffix, ouroboros-consensus/src/Ouroboros/
+ * Consensus/Storage/ChainDB/Impl/LgrDB.hs:350-368, ImmutableDB / VolatileDB
+ * replay, a ChainSync window across a boundary).  Entry j applies to
+ * first_slot[j] <= slot < first_slot[j + 1], the last entry to every slot from
+ * its first_slot up.  first_slot[0] must be 0, so every slot has an entry (a
+ * caller with nothing to say about early -- Byron -- slots puts any row
+ * there).  The kernels find a header's entry by binary search on its slot, at
+ * most 12 steps, inside the out-of-line mkSeed routine; the schedule is
+ * uploaded with the call (with each chunk of a pipelined call; 41 bytes per
+ * entry, about 170 KB at the cap) and nothing of it is kept afterwards.
+ * OURO_EINVAL before anything runs: k outside 1 .. OURO_EPOCHS_MAX,
+ * first_slot[0] != 0, first_slot not strictly increasing, first_slot or nonce
+ * NULL.  The schedule is an INPUT: computing the next epoch's nonce (TICKN)
+ * stays with the caller (ouro_nonce_fold is the tool). */
+#define OURO_EPOCHS_MAX 4096
+typedef struct ouro_epoch_nonces {
+  size_t k;                   /* 1 .. OURO_EPOCHS_MAX entries                      */
+  const uint64_t *first_slot; /* k, strictly increasing, first_slot[0] == 0        */
+  const uint8_t *nonce;       /* k x 32: eta0 of entry j                           */
+  const uint8_t *neutral;     /* k, may be NULL: 1 = NeutralNonce (row j ignored)  */
+} ouro_epoch_nonces;
+/* ouro_tpraos_verify_batch with mkSeed under the schedule: b->slot is
+ * required; b->epoch_nonce, b->eta_alpha and b->leader_alpha must be NULL
+ * (OURO_EINVAL otherwise).  Everything else -- OCERT sharing, the claimed
+ * outputs, eta_nonce, the host-path recompute after a device error -- is as
+ * ouro_tpraos_verify_batch; a one-entry schedule gives byte-identical results
+ * to that call with the entry's nonce as epoch_nonce (NULL for a neutral
+ * entry).  _host (declared with the host path below) is the same on the CPU.
+ * Out of scope: the latency plans (ouro_tpraos_plan_*, _lowlat) still take one
+ * eta0 -- a window through a plan is split at an epoch boundary -- and there
+ * is no device-pointer form. */
+int ouro_tpraos_verify_batch_epochs(const ouro_tpraos_batch *b, const ouro_epoch_nonces *e,
+                                    uint8_t *verdict, uint8_t *beta_eta, uint8_t *beta_leader);
 
 /* Raw header CBOR -> the SoA above.  Replaces the
  * per-header decode the reference runs on every header ChainSync receives
@@ -346,7 +385,8 @@ int ouro_integrity_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint6
  * VRF inputs: eta_alpha / leader_alpha (n x 32 each) when both are given,
  * otherwise derived on the device from each header's slot as the OVERLAY rule
  * does (mkSeed seedEta / seedL slot eta0, see ouro_tpraos_batch), with
- * epoch_nonce = eta0 (32 B; NULL = NeutralNonce; one eta0 per call).  The
+ * epoch_nonce = eta0 (32 B; NULL = NeutralNonce; one eta0 per call: a stream
+ * over several epochs goes to ouro_chain_verify_cbor with a schedule).  The
  * headers' claimed certifiedOutputs are compared (OURO_HDR_*_CLAIM_OK).
  * Outputs: status[i] = OURO_PACK_*; verdict[i] = OURO_HDR_* bits, 0 for a
  * header that does not slice; beta_eta / beta_leader (n x 64) and eta_nonce
@@ -434,6 +474,66 @@ int ouro_byron_pack_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *o
 int ouro_byron_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
                            const uint32_t *len, size_t n, int64_t protocol_magic,
                            uint8_t *status, uint8_t *verdict);
+/* A raw header stream across eras and epochs in ONE call: what ChainDB's
+ * re-validation of a stored suffix (LgrDB.hs:350-368), ImmutableDB /
+ * VolatileDB replay and ChainSync windows of a Cardano chain actually hold --
+ * Byron and Shelley-family headers in one buffer, Shelley slots over many
+ * epochs.  Headers as for ouro_tpraos_pack_cbor and ouro_byron_pack_cbor.
+ * proto[i] (required) = the header's protocol by its first few CBOR heads:
+ *   OURO_PROTO_PBFT iff it is a definite array(2) whose first item is the
+ *   definite uint 0 (HFC era 0), or a definite array(2) whose first item is an
+ *   array (Byron N2N v2), or #6.24 + a definite byte string whose payload
+ *   starts with a definite array(2) whose first item is a definite uint
+ *   (Byron N2N v1); OURO_PROTO_TPRAOS for everything else (truncated or
+ *   unreadable input included: the TPraos slicer's status says why).
+ * A header goes to exactly one slicer, so OURO_PACK_EBYRON and
+ * OURO_PACK_ESHELLEY never come out of this entry.
+ * PBFT rows: status / verdict exactly as ouro_byron_verify_cbor (1 for a
+ * verified regular header and for an epoch-boundary header, else 0); their
+ * beta_eta / beta_leader / eta_nonce rows are zero.  TPraos rows: everything
+ * exactly as ouro_tpraos_verify_cbor.  OURO_CHAIN_VALID(proto[i], verdict[i])
+ * is the per-header answer.
+ * VRF inputs: both eta_alpha and leader_alpha (n x 32, PBFT rows ignored) =
+ * explicit inputs; otherwise mkSeed on the device under `epochs`
+ * (ouro_epoch_nonces above), epochs == NULL = NeutralNonce everywhere.
+ * epochs together with alphas, or one alpha array only: OURO_EINVAL.  The
+ * other argument checks (spans, a zero period, the magic's range, NULLs, the
+ * device list) are those of the two single-era entries, before any work.
+ * How it runs: the pipeline of ouro_tpraos_verify_cbor; each header is
+ * classified while its bytes are gathered into pinned staging (no extra pass
+ * over the caller's buffer).  A chunk of one era runs that era's path
+ * unchanged; a mixed chunk uploads its bytes once and runs the Byron slicer +
+ * ByronDSIGN kernel over its PBFT headers and the TPraos slicer + header
+ * kernel over its TPraos headers on the chunk's stream, each through its own
+ * offset / length list, and both result sets are scattered back to the
+ * caller's order.  Per context only the index lists are kept beside the
+ * pipeline's buffers.  _host: the same on the host path, no device touched;
+ * _multi: contiguous shards over the listed devices, as the other _multi
+ * entries.  Out of scope: device-pointer forms; the latency plans. */
+#define OURO_PROTO_PBFT 0u
+#define OURO_PROTO_TPRAOS 1u
+#define OURO_CHAIN_VALID(proto, v) \
+  ((proto) == OURO_PROTO_PBFT ? (v) == 1 : ((v) & OURO_HDR_ALL_OK) == OURO_HDR_ALL_OK)
+int ouro_chain_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                           const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
+                           int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+                           const uint8_t *eta_alpha, const uint8_t *leader_alpha,
+                           uint8_t *proto, uint8_t *status, uint8_t *verdict,
+                           uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce);
+int ouro_chain_verify_cbor_host(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
+                                int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+                                const uint8_t *eta_alpha, const uint8_t *leader_alpha,
+                                uint8_t *proto, uint8_t *status, uint8_t *verdict,
+                                uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce);
+int ouro_chain_verify_cbor_multi(const int *devices, int ndev, const uint8_t *raw,
+                                 size_t raw_bytes, const uint64_t *off, const uint32_t *len,
+                                 size_t n, uint64_t slots_per_kes_period, int64_t protocol_magic,
+                                 const ouro_epoch_nonces *epochs, const uint8_t *eta_alpha,
+                                 const uint8_t *leader_alpha, uint8_t *proto, uint8_t *status,
+                                 uint8_t *verdict, uint8_t *beta_eta, uint8_t *beta_leader,
+                                 uint8_t *eta_nonce);
+
 /* (How ouro_byron_verify_cbor runs, since round 6: on the raw-CBOR pipeline
  * of ouro_tpraos_verify_cbor -- chunks gathered into pinned NUMA-local
  * staging, the device Byron slicer (the same cbor_byron.h parse as
@@ -604,6 +704,9 @@ int ouro_sum6kes_verify_batch_host(size_t n, const uint8_t *vk, const uint32_t *
                                    const uint32_t *msg_len, const uint8_t *sig, uint8_t *verdict);
 int ouro_tpraos_verify_batch_host(const ouro_tpraos_batch *b, uint8_t *verdict,
                                   uint8_t *beta_eta, uint8_t *beta_leader);
+int ouro_tpraos_verify_batch_epochs_host(const ouro_tpraos_batch *b, const ouro_epoch_nonces *e,
+                                         uint8_t *verdict, uint8_t *beta_eta,
+                                         uint8_t *beta_leader);
 int ouro_leader_check_batch_host(size_t n, const uint8_t *beta, const uint64_t *sigma_num,
                                  const uint64_t *sigma_den, int64_t act_log_hi,
                                  uint64_t act_log_lo, int f_is_one, uint8_t *verdict);

@@ -11,15 +11,16 @@ from ._native import DeviceError, NativeUnavailable
 from .byron import (ByronDSIGN, dlg_cert_message, pack_byron_cbor, parse_byron_header,
                     verify_byron_cbor, verify_byron_headers, verify_delegation_certs)
 from .dsign import Ed25519DSIGN
-from .header import verify_headers_cbor, verify_integrity_cbor
+from .header import verify_chain_cbor, verify_headers_cbor, verify_integrity_cbor
 from .kes import Sum6KES, kes_period
-from .tpraos import HeaderBatch, first_invalid, verify_headers, verify_headers_multi
+from .tpraos import EpochNonces, HeaderBatch, first_invalid, verify_headers, verify_headers_multi
 from .vrf import PraosVRF
 
 __all__ = [
     "ByronDSIGN",
     "DeviceError",
     "Ed25519DSIGN",
+    "EpochNonces",
     "HeaderBatch",
     "NativeUnavailable",
     "PraosVRF",
@@ -31,6 +32,7 @@ __all__ = [
     "parse_byron_header",
     "verify_byron_cbor",
     "verify_byron_headers",
+    "verify_chain_cbor",
     "verify_delegation_certs",
     "verify_headers",
     "verify_headers_cbor",

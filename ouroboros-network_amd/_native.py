@@ -35,6 +35,10 @@ HDR_LEADER_S_UNREDUCED = 0x80
 HDR_S_UNREDUCED = 0xC0
 VRF_STRICT_S = 0x1             # ouro_vrf03_verify_batch_flags: reject s >= L
 
+PROTO_PBFT = 0     # ouro_chain_verify_cbor proto[i]: a Byron header
+PROTO_TPRAOS = 1   # a Shelley-family header (and anything unreadable)
+EPOCHS_MAX = 4096  # OURO_EPOCHS_MAX
+
 LEADER_NO = 0
 LEADER_YES = 1
 LEADER_BADARG = 0xFF
@@ -77,6 +81,13 @@ class TPraosBatch(ctypes.Structure):
     ]
 
 
+class EpochNonces(ctypes.Structure):
+    """Mirror of ``ouro_epoch_nonces`` (include/ouro_verify.h)."""
+
+    _fields_ = [("k", ctypes.c_size_t), ("first_slot", ctypes.c_void_p),
+                ("nonce", ctypes.c_void_p), ("neutral", ctypes.c_void_p)]
+
+
 class ByronBatch(ctypes.Structure):
     """Mirror of ``ouro_byron_batch`` (include/ouro_verify.h)."""
 
@@ -116,6 +127,18 @@ SIGNATURES = {
     "ouro_tpraos_verify_batch_host": (_I, [ctypes.POINTER(TPraosBatch), _P, _P, _P]),
     "ouro_leader_check_batch_host": (_I, [_SZ, _P, _P, _P, ctypes.c_int64, ctypes.c_uint64, _I,
                                           _P]),
+    "ouro_tpraos_verify_batch_epochs": (_I, [ctypes.POINTER(TPraosBatch),
+                                             ctypes.POINTER(EpochNonces), _P, _P, _P]),
+    "ouro_tpraos_verify_batch_epochs_host": (_I, [ctypes.POINTER(TPraosBatch),
+                                                  ctypes.POINTER(EpochNonces), _P, _P, _P]),
+    "ouro_chain_verify_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64,
+                                    ctypes.POINTER(EpochNonces), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ouro_chain_verify_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64,
+                                         ctypes.POINTER(EpochNonces), _P, _P, _P, _P, _P, _P, _P,
+                                         _P]),
+    "ouro_chain_verify_cbor_multi": (_I, [_P, _I, _P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
+                                          ctypes.c_int64, ctypes.POINTER(EpochNonces), _P, _P, _P,
+                                          _P, _P, _P, _P, _P]),
     "ouro_debug_contexts": (_I, [_I, _P, _P]),
     "ouro_debug_lat_stamps": (_I, [_P]),
     "ouro_debug_clock_stamps": (_I, [_P, _I]),

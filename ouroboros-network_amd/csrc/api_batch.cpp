@@ -22,6 +22,32 @@
 using namespace ouro;
 using namespace ouro_rt;
 
+namespace ouro_rt {
+// ouro_epoch_nonces (include/ouro_verify.h) checked and packed as the block
+// the lane code reads (tpraos.h epoch_tab_*), 8-byte words for its alignment
+int epoch_tab_build(const ouro_epoch_nonces* e, std::vector<uint64_t>* tab) {
+  if (!e) return fail(OURO_EINVAL, "null epoch schedule");
+  if (e->k < 1 || e->k > OURO_EPOCHS_MAX)
+    return fail(OURO_EINVAL, "epoch schedule: k outside 1 .. OURO_EPOCHS_MAX");
+  if (!e->first_slot || !e->nonce) return fail(OURO_EINVAL, "epoch schedule: null first_slot or nonce");
+  if (e->first_slot[0] != 0) return fail(OURO_EINVAL, "epoch schedule: first_slot[0] must be 0");
+  for (size_t j = 1; j < e->k; j++)
+    if (e->first_slot[j] <= e->first_slot[j - 1])
+      return fail(OURO_EINVAL, "epoch schedule: first_slot not strictly increasing at entry " +
+                                   std::to_string(j));
+  const size_t k = e->k;
+  tab->assign(epoch_tab_bytes(k) / 8, 0);
+  uint8_t* t = reinterpret_cast<uint8_t*>(tab->data());
+  const uint32_t k32 = (uint32_t)k;
+  memcpy(t, &k32, 4);
+  memcpy(t + 16, e->first_slot, 8 * k);
+  memcpy(t + epoch_tab_nonce_off(k), e->nonce, 32 * k);
+  if (e->neutral)
+    for (size_t j = 0; j < k; j++) t[epoch_tab_neutral_off(k) + j] = e->neutral[j] ? 1 : 0;
+  return OURO_OK;
+}
+}  // namespace ouro_rt
+
 namespace {
 int ed_batch_host(size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                   const uint64_t* msg_off, const uint32_t* msg_len, uint8_t* verdict,
@@ -180,6 +206,21 @@ struct HdrOut {
   uint8_t *verdict, *beta_eta, *beta_leader, *eta_nonce;
 };
 
+// the argument checks of the two epochs entries; the schedule packed into *tab
+int check_epochs_batch(const ouro_tpraos_batch* b, const ouro_epoch_nonces* e,
+                       const uint8_t* verdict, std::vector<uint64_t>* tab) {
+  if (!b) return fail(OURO_EINVAL, "null batch");
+  int rc = epoch_tab_build(e, tab);
+  if (rc || b->n == 0) return rc;
+  if (!verdict) return fail(OURO_EINVAL, "null verdict");
+  if (!b->slot) return fail(OURO_EINVAL, "an epoch schedule needs the headers' slots (slot is null)");
+  if (b->epoch_nonce)
+    return fail(OURO_EINVAL, "epoch_nonce must be null beside an epoch schedule");
+  if (b->eta_alpha || b->leader_alpha)
+    return fail(OURO_EINVAL, "eta_alpha / leader_alpha must be null beside an epoch schedule");
+  return check_hdr_batch(b);
+}
+
 int pipe_drain(PipeSlot& p, const HdrOut& o) {
   if (!p.busy) return OURO_OK;
   p.busy = false;
@@ -192,14 +233,20 @@ int pipe_drain(PipeSlot& p, const HdrOut& o) {
   return OURO_OK;
 }
 
-int pipe_chunk(PipeSlot& p, const ouro_tpraos_batch* b, size_t lo, size_t m, const HdrOut& o) {
+// (tab: the call's epoch-nonce schedule block, or null; uploaded with every
+// chunk on the chunk's own stream -- at most ~170 KB beside ~100 MB of rows)
+int pipe_chunk(PipeSlot& p, const ouro_tpraos_batch* b, size_t lo, size_t m, const HdrOut& o,
+               const std::vector<uint64_t>* tab) {
   Stager sg{p.st};
   sg.bufs = p.in;
   sg.nbufs = (int)(sizeof(p.in) / sizeof(p.in[0]));
   int rc = stage_hdr(sg, b, lo, m, &p.staged);
   if (rc) return rc;
+  const uint64_t* dtab = tab ? sg.up(tab->data(), tab->size()) : nullptr;
+  if (sg.rc) return sg.rc;
   const StagedHdr& s = p.staged;
-  if ((rc = launch_hdr(p.st, s.d, s.ver, s.be, s.bl))) return rc;
+  if ((rc = launch_hdr(p.st, s.d, s.ver, s.be, s.bl, reinterpret_cast<const uint8_t*>(dtab))))
+    return rc;
   if (p.h_cap < kOutRow * m) {
     if (p.h_out) OURO_HIP(hipHostFree(p.h_out));
     p.h_out = nullptr;
@@ -229,7 +276,8 @@ size_t host_chunk(DeviceState* ds) {
   return v >= 0 ? (size_t)v : (size_t)ds->max_blocks[kHdr] * kBlock;
 }
 
-int hdr_batch_pipelined(const ouro_tpraos_batch* b, size_t chunk, const HdrOut& o) {
+int hdr_batch_pipelined(const ouro_tpraos_batch* b, size_t chunk, const HdrOut& o,
+                        const std::vector<uint64_t>* tab) {
   int dev, rc = current_device(&dev);
   if (rc) return rc;
   Pipe* pp;
@@ -238,7 +286,7 @@ int hdr_batch_pipelined(const ouro_tpraos_batch* b, size_t chunk, const HdrOut& 
   for (size_t lo = 0; lo < b->n && !rc; lo += chunk, c++) {
     PipeSlot& p = pp->s[c & 1];
     rc = pipe_drain(p, o);
-    if (!rc) rc = pipe_chunk(p, b, lo, std::min(chunk, b->n - lo), o);
+    if (!rc) rc = pipe_chunk(p, b, lo, std::min(chunk, b->n - lo), o, tab);
   }
   // older chunk first; on an error, still wait for everything in flight
   for (int k = 0; k < 2; k++) {
@@ -255,7 +303,8 @@ int hdr_batch_pipelined(const ouro_tpraos_batch* b, size_t chunk, const HdrOut& 
 
 // one synchronous launch of the whole batch (throughput kernel, or the
 // latency-mode kernels with lowlat), results copied out after the sync
-int hdr_batch_once(const ouro_tpraos_batch* b, const HdrOut& o, bool lowlat) {
+int hdr_batch_once(const ouro_tpraos_batch* b, const HdrOut& o, bool lowlat,
+                   const std::vector<uint64_t>* tab = nullptr) {
   const size_t n = b->n;
   hipStream_t st;
   int rc = thread_stream(&st);
@@ -265,6 +314,8 @@ int hdr_batch_once(const ouro_tpraos_batch* b, const HdrOut& o, bool lowlat) {
   Stager sg{st};
   StagedHdr s;
   if ((rc = stage_hdr(sg, b, 0, n, &s))) return rc;
+  const uint64_t* dtab = tab ? sg.up(tab->data(), tab->size()) : nullptr;
+  if (sg.rc) return sg.rc;
   if (lowlat) {
     // {n, option bits, generation (arrive_last; res is zeroed below), 0}
     const uint32_t nw[4] = {(uint32_t)n, batch_opts(s.d), 1u, 0u};
@@ -277,7 +328,8 @@ int hdr_batch_once(const ouro_tpraos_batch* b, const HdrOut& o, bool lowlat) {
     OURO_HIP(hipMemsetAsync(res, 0, sizeof(int32_t) * slot_region_words(n, kLatResWords), st));
     // (nw is read by the H2D above; this frame outlives the sync below)
     if ((rc = launch_lowlat(st, s.d, d_n, n, res, scr, s.ver, s.be, s.bl))) return rc;
-  } else if ((rc = launch_hdr(st, s.d, s.ver, s.be, s.bl))) {
+  } else if ((rc = launch_hdr(st, s.d, s.ver, s.be, s.bl,
+                              reinterpret_cast<const uint8_t*>(dtab)))) {
     return rc;
   }
   std::vector<uint8_t> tv(n), te(o.beta_eta ? 64 * n : 0), tl(o.beta_leader ? 64 * n : 0),
@@ -308,8 +360,30 @@ int ouro_tpraos_verify_batch(const ouro_tpraos_batch* b, uint8_t* verdict, uint8
   if ((rc = device_state(&ds))) return rc;
   const HdrOut o{verdict, beta_eta, beta_leader, b->eta_nonce};
   const size_t chunk = host_chunk(ds);
-  rc = chunk && b->n > chunk ? hdr_batch_pipelined(b, chunk, o) : hdr_batch_once(b, o, false);
+  rc = chunk && b->n > chunk ? hdr_batch_pipelined(b, chunk, o, nullptr)
+                             : hdr_batch_once(b, o, false);
   return or_host(rc, [&] { return ouro_host::hdr_batch(b, verdict, beta_eta, beta_leader); });
+}
+
+// The same under an epoch-nonce schedule: mkSeed's eta0 looked up per header
+// by its slot (tpraos.h hdr_mkseed, kOptEpochs), so one call verifies a batch
+// that crosses epoch boundaries.  Every argument check runs before anything
+// else does.
+int ouro_tpraos_verify_batch_epochs(const ouro_tpraos_batch* b, const ouro_epoch_nonces* e,
+                                    uint8_t* verdict, uint8_t* beta_eta, uint8_t* beta_leader) {
+  std::vector<uint64_t> tab;
+  int rc = check_epochs_batch(b, e, verdict, &tab);
+  if (rc || b->n == 0) return rc;
+  DeviceState* ds;
+  if ((rc = device_state(&ds))) return rc;
+  const HdrOut o{verdict, beta_eta, beta_leader, b->eta_nonce};
+  const size_t chunk = host_chunk(ds);
+  rc = chunk && b->n > chunk ? hdr_batch_pipelined(b, chunk, o, &tab)
+                             : hdr_batch_once(b, o, false, &tab);
+  return or_host(rc, [&] {
+    return ouro_host::hdr_batch(b, verdict, beta_eta, beta_leader,
+                                reinterpret_cast<const uint8_t*>(tab.data()));
+  });
 }
 
 // ---- latency mode (ChainSync windows) ----
@@ -655,6 +729,16 @@ int ouro_tpraos_verify_batch_host(const ouro_tpraos_batch* b, uint8_t* verdict,
   if (rc) return rc;
   if ((rc = check_spans(b->n, b->body_off, b->body_len, b->body, "body"))) return rc;
   return ouro_host::hdr_batch(b, verdict, beta_eta, beta_leader);
+}
+int ouro_tpraos_verify_batch_epochs_host(const ouro_tpraos_batch* b, const ouro_epoch_nonces* e,
+                                         uint8_t* verdict, uint8_t* beta_eta,
+                                         uint8_t* beta_leader) {
+  std::vector<uint64_t> tab;
+  int rc = check_epochs_batch(b, e, verdict, &tab);
+  if (rc || b->n == 0) return rc;
+  if ((rc = check_spans(b->n, b->body_off, b->body_len, b->body, "body"))) return rc;
+  return ouro_host::hdr_batch(b, verdict, beta_eta, beta_leader,
+                              reinterpret_cast<const uint8_t*>(tab.data()));
 }
 int ouro_leader_check_batch_host(size_t n, const uint8_t* beta, const uint64_t* sigma_num,
                                  const uint64_t* sigma_den, int64_t act_log_hi,

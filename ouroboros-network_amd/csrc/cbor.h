@@ -201,6 +201,41 @@ OURO_HD inline int bytes_at(const Cur& c, uint64_t i, uint64_t want, const uint8
   return kBytesOk;
 }
 
+// The era of a raw header from its first few CBOR heads (bounded: at most
+// four heads are read, nothing is walked): OURO_PROTO_PBFT for the three Byron
+// wire forms of cbor_byron.h, OURO_PROTO_TPRAOS for everything else.  PBFT iff
+//   * a definite array(2) whose first item is a definite uint equal to 0
+//     (the HFC era-0 form, F3), or
+//   * a definite array(2) whose first item is an array (Byron N2N v2, F2:
+//     [[kind, size], ...]), or
+//   * #6.24 + a definite byte string whose payload starts with a definite
+//     array(2) whose first item is a definite uint (Byron N2N v1, F1:
+//     [kind, header]; a TPraos payload is [header_body, kes_sig], an array first).
+// Truncated or unreadable input, [era >= 1, ...] and #6.24([array, ...]) are
+// TPraos: the TPraos slicer's status then says what is wrong with them.  So
+// the combined entry (ouro_chain_verify_cbor) sends a header to exactly one
+// slicer, and OURO_PACK_EBYRON (the TPraos slicer on era 0) and
+// OURO_PACK_ESHELLEY (the Byron slicer on era >= 1) never come out of it.
+// header.py era_class is the same rule (tests/test_chain_cbor.py pins the two
+// against each other and against both Python slicers).
+OURO_HD inline uint32_t era_class(const uint8_t* raw, uint64_t len) {
+  const Cur c{raw, len};
+  int mt, mt1;
+  uint64_t arg, a1, j, j1;
+  bool ind, i1;
+  if (!head(c, 0, &mt, &arg, &j, &ind)) return OURO_PROTO_TPRAOS;
+  if (mt == 4 && !ind && arg == 2) {
+    if (!head(c, j, &mt1, &a1, &j1, &i1)) return OURO_PROTO_TPRAOS;
+    if (mt1 == 0) return (!i1 && a1 == 0) ? OURO_PROTO_PBFT : OURO_PROTO_TPRAOS;
+    return mt1 == 4 ? OURO_PROTO_PBFT : OURO_PROTO_TPRAOS;
+  }
+  if (mt != 6 || ind || arg != 24) return OURO_PROTO_TPRAOS;
+  if (!head(c, j, &mt, &arg, &j, &ind) || mt != 2 || ind) return OURO_PROTO_TPRAOS;
+  if (!head(c, j, &mt, &arg, &j, &ind) || mt != 4 || ind || arg != 2) return OURO_PROTO_TPRAOS;
+  if (!head(c, j, &mt1, &a1, &j1, &i1)) return OURO_PROTO_TPRAOS;
+  return (mt1 == 0 && !i1) ? OURO_PROTO_PBFT : OURO_PROTO_TPRAOS;
+}
+
 struct Out {
   uint8_t *issuer_vk, *vrf_vk, *eta_proof, *leader_proof, *hot_vk, *sigma, *kes_sig;
   uint8_t *eta_output, *leader_output;

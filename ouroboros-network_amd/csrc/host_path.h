@@ -34,8 +34,10 @@ int vrf_batch(size_t n, const uint8_t* pk, const uint8_t* proof, const uint8_t* 
               uint32_t flags);
 int kes_batch(size_t n, const uint8_t* vk, const uint32_t* t, const uint8_t* msg,
               const uint64_t* off, const uint32_t* len, const uint8_t* sig, uint8_t* verdict);
+// epochs: an epoch-nonce schedule block in host memory (tpraos.h epoch_tab_*),
+// looked up per header by its slot, or null
 int hdr_batch(const ouro_tpraos_batch* b, uint8_t* verdict, uint8_t* beta_eta,
-              uint8_t* beta_leader);
+              uint8_t* beta_leader, const uint8_t* epochs = nullptr);
 int leader_batch(size_t n, const uint8_t* beta, const uint64_t* num, const uint64_t* den,
                  int64_t act_log_hi, uint64_t act_log_lo, int f_is_one, uint8_t* verdict);
 // proof_to_hash without verification: OURO_OK and out written, or OURO_INVALID

@@ -180,11 +180,15 @@ int kes_batch(size_t n, const uint8_t* vk, const uint32_t* t, const uint8_t* msg
   });
 }
 
-int hdr_batch(const ouro_tpraos_batch* b, uint8_t* verdict, uint8_t* beta_eta,
-              uint8_t* beta_leader) {
+int hdr_batch(const ouro_tpraos_batch* b_in, uint8_t* verdict, uint8_t* beta_eta,
+              uint8_t* beta_leader, const uint8_t* epochs) {
   const int32_t* bt = btab();
+  // (as kernels.hip launch_hdr: the schedule where the single eta0 would be)
+  ouro_tpraos_batch bb = *b_in;
+  if (epochs) bb.epoch_nonce = epochs;
+  const ouro_tpraos_batch* b = &bb;
   const size_t n = b->n;
-  const uint32_t opts = batch_opts(*b);
+  const uint32_t opts = batch_opts(*b) | (epochs ? kOptEpochs : 0u);
   // the finish re-reads both outputs for the claimed-output bits / eta nonce
   std::unique_ptr<uint8_t[]> te, tl;
   if (!beta_eta) {

@@ -277,12 +277,13 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tprao
                                                              const int32_t* __restrict__ btab,
                                                              const uint32_t* __restrict__ rep,
                                                              const uint8_t* __restrict__ ocert_ok,
-                                                             const uint32_t* __restrict__ ocert_count) {
+                                                             const uint32_t* __restrict__ ocert_count,
+                                                             uint32_t xopts) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nth = (size_t)gridDim.x * blockDim.x;
   const Slot lane = slot_of(scratch, tid, kHdrLaneWords);
   const Slot res = lane + kLaneWords;
-  const uint32_t opts = batch_opts(b);
+  const uint32_t opts = batch_opts(b) | xopts;  // xopts: kOptEpochs (launch_hdr)
   const bool shared = ocert_count != nullptr && *ocert_count <= kOcertShareMax(b.n);
   const int core0 = shared ? kCoreKes : kCoreOcert;
 #if OURO_CLOCK_STAMPS
@@ -351,9 +352,10 @@ constexpr int kHdrResWords = round_slot(kResWords);
 __global__ void __launch_bounds__(kBlock, OURO_PRE_WAVES) k_hdr_pre(ouro_tpraos_batch b, size_t base,
                                                                size_t count, size_t chunk,
                                                                int32_t* tasks, int32_t* res_buf,
-                                                               const int32_t* __restrict__ btab) {
+                                                               const int32_t* __restrict__ btab,
+                                                               uint32_t xopts) {
   const size_t nth = (size_t)gridDim.x * blockDim.x;
-  const uint32_t opts = batch_opts(b);
+  const uint32_t opts = batch_opts(b) | xopts;
   for (size_t li = (size_t)blockIdx.x * blockDim.x + threadIdx.x; li < count; li += nth) {
     const size_t i = base + li;
     const Slot res = slot_of(res_buf, li, kHdrResWords);
@@ -380,9 +382,10 @@ __global__ void __launch_bounds__(kBlock, OURO_POST_WAVES) k_hdr_post(ouro_tprao
                                                                 int32_t* tasks, int32_t* res_buf,
                                                                 uint8_t* __restrict__ verdict,
                                                                 uint8_t* __restrict__ beta_eta,
-                                                                uint8_t* __restrict__ beta_leader) {
+                                                                uint8_t* __restrict__ beta_leader,
+                                                                uint32_t xopts) {
   const size_t nth = (size_t)gridDim.x * blockDim.x;
-  const uint32_t opts = batch_opts(b);
+  const uint32_t opts = batch_opts(b) | xopts;
   for (size_t li = (size_t)blockIdx.x * blockDim.x + threadIdx.x; li < count; li += nth) {
     const size_t i = base + li;
     const Slot res = slot_of(res_buf, li, kHdrResWords);
@@ -728,11 +731,21 @@ int launch_kes(hipStream_t st, size_t n, const uint8_t* vk, const uint32_t* t, c
 }
 
 
-int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b, uint8_t* verdict, uint8_t* be,
-               uint8_t* bl) {
+// epochs (device memory, tpraos.h EpochTab block; null = none): the batch's
+// slots are looked up in it per header (kOptEpochs); the kernels find it where
+// the single eta0 would be
+int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b_in, uint8_t* verdict, uint8_t* be,
+               uint8_t* bl, const uint8_t* epochs) {
   DeviceState* ds;
   int rc = device_state(&ds);
   if (rc) return rc;
+  ouro_tpraos_batch b = b_in;
+  uint32_t xopts = 0;
+  if (epochs) {
+    if (!b.slot) return fail(OURO_EINVAL, "an epoch schedule needs the headers' slots");
+    b.epoch_nonce = epochs;
+    xopts = kOptEpochs;
+  }
   int grid;
   int32_t* scr;
   if (split_launch()) {
@@ -753,11 +766,11 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b, uint8_t* verdict, uin
     for (size_t base = 0; base < b.n; base += chunk) {
       const size_t count = std::min(chunk, b.n - base);
       hipLaunchKernelGGL(k_hdr_pre, dim3(gpp), dim3(kBlock), 0, st, b, base, count, chunk, tasks,
-                         res, ds->btab);
+                         res, ds->btab, xopts);
       hipLaunchKernelGGL(k_hdr_dsm, dim3(gd), dim3(kBlock), 0, st, count, chunk, (int)kHdrCores,
                          tasks, ds->btab);
       hipLaunchKernelGGL(k_hdr_post, dim3(gpo), dim3(kBlock), 0, st, b, base, count, chunk, tasks,
-                         res, verdict, be, bl);
+                         res, verdict, be, bl, xopts);
       if ((rc = launch_check())) return rc;
     }
     ctx().ocert[st].last = nullptr;
@@ -805,7 +818,7 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b, uint8_t* verdict, uin
     return rc;
   }
   hipLaunchKernelGGL(k_tpraos_verify, dim3(grid), dim3(kBlock), 0, st, b, verdict, be, bl, scr,
-                     ds->btab, rep, ocert_ok, count);
+                     ds->btab, rep, ocert_ok, count, xopts);
   return launch_check();
 }
 

@@ -39,8 +39,9 @@ int launch_vrf(hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* proof
                uint8_t* verdict, uint32_t flags = 0);
 int launch_kes(hipStream_t st, size_t n, const uint8_t* vk, const uint32_t* t, const uint8_t* msg,
                const uint64_t* off, const uint32_t* len, const uint8_t* sig, uint8_t* verdict);
+// epochs: a device epoch-nonce schedule (tpraos.h epoch_tab_*), or null
 int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b, uint8_t* verdict, uint8_t* be,
-               uint8_t* bl);
+               uint8_t* bl, const uint8_t* epochs = nullptr);
 int launch_leader(hipStream_t st, size_t n, const uint8_t* beta, const uint64_t* num,
                   const uint64_t* den, int64_t lhi, uint64_t llo, int f_is_one,
                   uint8_t* verdict);

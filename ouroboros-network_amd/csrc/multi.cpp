@@ -210,6 +210,7 @@ RawCall raw_shard(const RawCall& c, size_t lo, size_t m) {
   if (c.be) s.be = c.be + 64 * lo;
   if (c.bl) s.bl = c.bl + 64 * lo;
   if (c.nonce) s.nonce = c.nonce + 32 * lo;
+  if (c.proto) s.proto = c.proto + lo;  // (the epoch schedule is shared)
   return s;
 }
 
@@ -218,8 +219,7 @@ RawCall raw_shard(const RawCall& c, size_t lo, size_t m) {
 // slots, the host-path recompute of that shard after a device error)
 int raw_verify_multi(const RawCall& c, const int* devices, int ndev) {
   if (c.n == 0) return OURO_OK;
-  if (!c.raw || !c.off || !c.len || !c.status || !c.verdict)
-    return fail(OURO_EINVAL, "null argument");
+  if (int rc0 = raw_check(c)) return rc0;
   for (size_t i = 0; i < c.n; i++)  // every span inside raw before any shard starts
     if (c.off[i] > c.raw_bytes || c.raw_bytes - c.off[i] < c.len[i])
       return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
@@ -306,6 +306,29 @@ int ouro_integrity_verify_cbor_multi(const int* devices, int ndev, const uint8_t
   if (n && slots_per_kes_period == 0) return fail(OURO_EINVAL, "zero slots per KES period");
   RawCall c{kRawKes, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, nullptr,
             nullptr, status, verdict, nullptr, nullptr, nullptr};
+  return raw_verify_multi(c, devices, ndev);
+}
+
+// The combined entry (raw_pipe.cpp ouro_chain_verify_cbor) sharded like the
+// others: each shard classifies and verifies its own headers; the epoch
+// schedule is validated and packed once and shared by every shard.
+int ouro_chain_verify_cbor_multi(const int* devices, int ndev, const uint8_t* raw,
+                                 size_t raw_bytes, const uint64_t* off, const uint32_t* len,
+                                 size_t n, uint64_t slots_per_kes_period, int64_t protocol_magic,
+                                 const ouro_epoch_nonces* epochs, const uint8_t* eta_alpha,
+                                 const uint8_t* leader_alpha, uint8_t* proto, uint8_t* status,
+                                 uint8_t* verdict, uint8_t* beta_eta, uint8_t* beta_leader,
+                                 uint8_t* eta_nonce) {
+  RawCall c{kRawChain, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, eta_alpha,
+            leader_alpha, status, verdict, beta_eta, beta_leader, eta_nonce, protocol_magic,
+            proto};
+  if (n == 0) return OURO_OK;
+  std::vector<uint64_t> tab;
+  if (epochs) {
+    if (int rc = epoch_tab_build(epochs, &tab)) return rc;
+    c.epochs = reinterpret_cast<const uint8_t*>(tab.data());
+    c.epochs_bytes = 8 * tab.size();
+  }
   return raw_verify_multi(c, devices, ndev);
 }
 

@@ -52,6 +52,11 @@ using namespace ouro_rt;
 //     neighbouring chunks share the CUs as each one's waves retire.
 // A device error stops the pipeline (everything in flight is waited for) and
 // the whole batch is recomputed on the host path (raw_host).
+// The combined entry (kRawChain, ouro_chain_verify_cbor) classifies every
+// header while it is gathered (cbor.h era_class): a chunk of one era runs that
+// era's path above, a mixed chunk both slicers and both kernels on its one
+// upload, each over its own offset / length list (raw_stage, raw_launch), and
+// raw_drain scatters the two result sets back to the caller's order.
 namespace {
 constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kRawChunkBytes = (size_t)96 << 20;
@@ -62,19 +67,26 @@ struct RawChunk {
 };
 
 // the pinned / device input block of a chunk of m headers and `bytes` raw bytes
+// (tab: the call's epoch-nonce schedule block, uploaded with every chunk)
 struct RawIn {
-  size_t off, len, eta0, alpha, raw, total;
+  size_t off, len, eta0, alpha, tab, raw, total;
 };
-RawIn raw_in(size_t m, size_t bytes, bool alphas) {
+RawIn raw_in(size_t m, size_t bytes, bool alphas, size_t tab_bytes) {
   RawIn l;
   l.off = 0;
   l.len = a16(8 * m);
   l.eta0 = l.len + a16(4 * m);
   l.alpha = l.eta0 + 32;
-  l.raw = a16(l.alpha + (alphas ? 64 * m : 0));
+  l.tab = a16(l.alpha + (alphas ? 64 * m : 0));
+  l.raw = l.tab + a16(tab_bytes);
   l.total = l.raw + a16(std::max<size_t>(bytes, 16));
   return l;
 }
+// the Byron results of a mixed chunk (mb PBFT headers), behind the TPraos block
+struct RawOutB {
+  size_t status, verdict, total;
+};
+RawOutB raw_out_b(size_t mb) { return RawOutB{0, a16(mb), a16(mb) + a16(mb)}; }
 // its result block: status | verdict | beta_eta | beta_leader | eta_nonce | slot
 struct RawOut {
   size_t status, verdict, be, bl, nonce, slot, total;
@@ -92,7 +104,7 @@ RawOut raw_out(size_t m) {
 }
 // bytes of the result block copied back
 size_t raw_out_bytes(const RawCall& c, const RawOut& o, size_t m) {
-  if (c.kind != kRawHdr) return o.verdict + m;
+  if (c.kind != kRawHdr && c.kind != kRawChain) return o.verdict + m;
   if (c.nonce) return o.slot;
   if (c.bl) return o.nonce;
   if (c.be) return o.bl;
@@ -159,7 +171,8 @@ int pinned_at_least(uint8_t** p, size_t* cap, size_t bytes) {
 // the chunk's header spans from the caller's buffer into the slot's pinned block
 int raw_stage(RawSlot& s, const RawCall& c, const RawChunk& k, int width) {
   const bool alphas = c.ea != nullptr;
-  const RawIn L = raw_in(k.m, k.bytes, alphas);
+  const bool chain = c.kind == kRawChain;
+  const RawIn L = raw_in(k.m, k.bytes, alphas, c.epochs_bytes);
   int rc = pinned_at_least(&s.h_in, &s.h_in_cap, L.total + L.total / 8);
   if (rc) return rc;
   uint64_t* noff = reinterpret_cast<uint64_t*>(s.h_in + L.off);
@@ -170,6 +183,7 @@ int raw_stage(RawSlot& s, const RawCall& c, const RawChunk& k, int width) {
   }
   memcpy(s.h_in + L.len, c.len + k.lo, 4 * k.m);
   if (c.eta0) memcpy(s.h_in + L.eta0, c.eta0, 32);
+  if (c.epochs) memcpy(s.h_in + L.tab, c.epochs, c.epochs_bytes);
   if (alphas) {
     memcpy(s.h_in + L.alpha, c.ea + 32 * k.lo, 32 * k.m);
     memcpy(s.h_in + L.alpha + 32 * k.m, c.la + 32 * k.lo, 32 * k.m);
@@ -186,74 +200,154 @@ int raw_stage(RawSlot& s, const RawCall& c, const RawChunk& k, int width) {
       size_t j = i + 1;
       while (j < b && c.off[k.lo + j] == src + bytes) bytes += c.len[k.lo + j++];
       memcpy(dst + noff[i], c.raw + src, bytes);
+      // the combined entry: each header's era from the bytes just copied
+      // (in cache; no pass of its own over the caller's buffer)
+      if (chain)
+        for (size_t q = i; q < j; q++)
+          c.proto[k.lo + q] = (uint8_t)cbor::era_class(dst + noff[q], c.len[k.lo + q]);
       i = j;
     }
   });
-  return r ? fail(OURO_EDEVICE, "raw CBOR gather failed") : OURO_OK;
+  if (r) return fail(OURO_EDEVICE, "raw CBOR gather failed");
+  s.mode = c.kind == kRawByron ? kModeByron : kModeTpraos;
+  s.mt = k.m;
+  if (!chain) return OURO_OK;
+  const uint8_t* pr = c.proto + k.lo;
+  size_t mt = 0;
+  for (size_t i = 0; i < k.m; i++) mt += pr[i] == OURO_PROTO_TPRAOS;
+  s.mt = mt;
+  if (mt == k.m) return OURO_OK;  // one era: that era's path, unchanged
+  if (mt == 0) {
+    s.mode = kModeByron;
+    return OURO_OK;
+  }
+  // A mixed chunk.  The bytes stay where the gather put them; the offset and
+  // length lists are reordered by class -- the TPraos headers' entries first,
+  // then the PBFT headers', each class in the caller's order -- so each
+  // slicer runs over one contiguous list, and idx says where a class's row
+  // belongs in the caller's arrays.
+  s.mode = kModeMixed;
+  std::vector<uint64_t> o2;
+  try {  // (no exception crosses the C ABI)
+    s.idx.resize(k.m);
+    o2.resize(k.m);
+  } catch (const std::bad_alloc&) {
+    return fail(OURO_EDEVICE, "raw CBOR gather: out of host memory");
+  }
+  size_t at_t = 0, at_b = mt;
+  for (size_t i = 0; i < k.m; i++) {
+    const size_t j = pr[i] == OURO_PROTO_TPRAOS ? at_t++ : at_b++;
+    s.idx[j] = (uint32_t)i;
+    o2[j] = noff[i];
+  }
+  memcpy(noff, o2.data(), 8 * k.m);
+  uint32_t* nlen = reinterpret_cast<uint32_t*>(s.h_in + L.len);
+  for (size_t j = 0; j < k.m; j++) nlen[j] = c.len[k.lo + s.idx[j]];
+  if (alphas)
+    for (size_t j = 0; j < mt; j++) {
+      memcpy(s.h_in + L.alpha + 32 * j, c.ea + 32 * (k.lo + s.idx[j]), 32);
+      memcpy(s.h_in + L.alpha + 32 * k.m + 32 * j, c.la + 32 * (k.lo + s.idx[j]), 32);
+    }
+  return OURO_OK;
 }
 
-// the slot's stream: upload, device slicer, kernel, results back
+// the Byron slicer into `arena`, then the Ed25519 kernel with ByronDSIGN
+// acceptance (cardano-crypto: SURVEY.md App. B.5), over the mb headers the
+// lists doff / dlen address inside the chunk's raw bytes
+int raw_launch_byron(RawSlot& s, const RawCall& c, const uint8_t* draw, size_t raw_bytes,
+                     const uint64_t* doff, const uint32_t* dlen, size_t mb, uint8_t* arena,
+                     uint8_t* dstatus, uint8_t* dverdict) {
+  const size_t blocks = std::min<size_t>((mb + kBlock - 1) / kBlock, 4096);
+  const cbor::ByronLayout bl = cbor::byron_layout(mb, raw_bytes + cbor::kByronMsgExtra * mb);
+  const cbor::ByronOut o = cbor::byron_arena_out(arena, bl);
+  launch_byron_pack(s.st, (unsigned)blocks, draw, raw_bytes, doff, dlen, mb, c.magic, o, dstatus);
+  int rc;
+  if ((rc = launch_check())) return rc;
+  return launch_ed(s.st, mb, o.pk, o.sig, o.msg, o.msg_off, o.msg_len, dverdict, 1);
+}
+
+// the TPraos slicer into `arena`, then the header kernel (or the Sum6KES
+// kernel, for integrity) over the mt headers of the lists doff / dlen;
+// results into the RawOut block at dout.  dea / dla: the explicit VRF inputs
+// of those headers, or null: mkSeed from the sliced slots under the epoch
+// schedule dtab, else under deta0 (null: NeutralNonce)
+int raw_launch_tpraos(RawSlot& s, const RawCall& c, const uint8_t* draw, size_t raw_bytes,
+                      const uint64_t* doff, const uint32_t* dlen, size_t mt, uint8_t* arena,
+                      uint8_t* dout, const uint8_t* dea, const uint8_t* dla,
+                      const uint8_t* deta0, const uint8_t* dtab) {
+  const RawOut O = raw_out(mt);
+  const size_t blocks = std::min<size_t>((mt + kBlock - 1) / kBlock, 4096);
+  uint64_t* dslot = reinterpret_cast<uint64_t*>(dout + O.slot);
+  const bool seeds = c.kind != kRawKes && !dea;
+  const cbor::Out o = cbor::arena_out(arena, mt, seeds ? dslot : nullptr, nullptr);
+  launch_tpraos_pack(s.st, (unsigned)blocks, draw, raw_bytes, doff, dlen, mt, c.spkp, o,
+                     dout + O.status);
+  int rc;
+  if ((rc = launch_check())) return rc;
+  ouro_tpraos_batch b{};
+  cbor::batch_from(&b, o, draw, mt);
+  if (c.kind == kRawKes)
+    return launch_kes(s.st, mt, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig,
+                      dout + O.verdict);
+  if (dea) {
+    b.eta_alpha = dea;
+    b.leader_alpha = dla;
+  } else {
+    b.slot = dslot;
+    b.epoch_nonce = deta0;
+  }
+  if (c.nonce) b.eta_nonce = dout + O.nonce;
+  return launch_hdr(s.st, b, dout + O.verdict, dout + O.be, dout + O.bl, dea ? nullptr : dtab);
+}
+
+// the slot's stream: upload, device slicer(s), kernel(s), results back
 int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
   const bool alphas = c.ea != nullptr;
-  const RawIn L = raw_in(k.m, k.bytes, alphas);
-  const RawOut O = raw_out(k.m);
-  const size_t back = raw_out_bytes(c, O, k.m);
+  const RawIn L = raw_in(k.m, k.bytes, alphas, c.epochs_bytes);
+  const size_t mt = s.mode == kModeByron ? 0 : s.mt, mb = k.m - mt;
+  const RawOut O = raw_out(mt ? mt : k.m);
+  const RawOutB OB = raw_out_b(mb);
+  // bytes copied back: one era's block, or a mixed chunk's two
+  const size_t back = mt ? raw_out_bytes(c, O, mt) : O.verdict + k.m;
+  const size_t back_b = s.mode == kModeMixed ? OB.verdict + mb : 0;
+  const size_t arena_t = mt ? a16(ouro_tpraos_pack_bytes(mt)) + 64 : 0;
+  const cbor::ByronLayout bl = cbor::byron_layout(mb, k.bytes + cbor::kByronMsgExtra * mb);
   int rc;
-  if ((rc = ensure(s.d_in, L.total)) || (rc = ensure(s.d_arena, ouro_tpraos_pack_bytes(k.m))) ||
-      (rc = ensure(s.d_out, O.total)) || (rc = pinned_at_least(&s.h_out, &s.h_out_cap, back)))
+  if ((rc = ensure(s.d_in, L.total)) ||
+      (rc = ensure(s.d_arena, arena_t + (mb ? bl.total + 64 : 0))) ||
+      (rc = ensure(s.d_out, a16(O.total) + (back_b ? OB.total : 0))) ||
+      (rc = pinned_at_least(&s.h_out, &s.h_out_cap, a16(back) + back_b)))
     return rc;
   uint8_t* din = static_cast<uint8_t*>(s.d_in.p);
   uint8_t* dout = static_cast<uint8_t*>(s.d_out.p);
+  uint8_t* darena = static_cast<uint8_t*>(s.d_arena.p);
   OURO_HIP(hipMemcpyAsync(din, s.h_in, L.total, hipMemcpyHostToDevice, s.st));
-  const size_t blocks = std::min<size_t>((k.m + kBlock - 1) / kBlock, 4096);
-  if (c.kind == kRawByron) {
-    // the device Byron slicer into the slot's arena, then the Ed25519 kernel
-    // with ByronDSIGN acceptance (cardano-crypto: SURVEY.md App. B.5)
-    const cbor::ByronLayout bl = cbor::byron_layout(k.m, k.bytes + cbor::kByronMsgExtra * k.m);
-    if ((rc = ensure(s.d_arena, bl.total + 64))) return rc;
-    const cbor::ByronOut o = cbor::byron_arena_out(cbor::arena_base(s.d_arena.p), bl);
-    launch_byron_pack(s.st, (unsigned)blocks, din + L.raw, k.bytes,
-                      reinterpret_cast<const uint64_t*>(din + L.off),
-                      reinterpret_cast<const uint32_t*>(din + L.len), k.m, c.magic, o,
-                      dout + O.status);
-    if ((rc = launch_check())) return rc;
-    if ((rc = launch_ed(s.st, k.m, o.pk, o.sig, o.msg, o.msg_off, o.msg_len, dout + O.verdict, 1)))
-      return rc;
-    OURO_HIP(hipMemcpyAsync(s.h_out, dout, back, hipMemcpyDeviceToHost, s.st));
-    OURO_HIP(hipEventRecord(s.done, s.st));
-    s.lo = k.lo;
-    s.m = k.m;
-    s.busy = true;
-    return OURO_OK;
-  }
-  uint64_t* dslot = reinterpret_cast<uint64_t*>(dout + O.slot);
-  const bool seeds = c.kind == kRawHdr && !alphas;
-  const cbor::Out o = cbor::arena_out(cbor::arena_base(s.d_arena.p), k.m, seeds ? dslot : nullptr,
-                                      nullptr);
   const uint8_t* draw = din + L.raw;
-  launch_tpraos_pack(s.st, (unsigned)blocks, draw, k.bytes,
-                     reinterpret_cast<const uint64_t*>(din + L.off),
-                     reinterpret_cast<const uint32_t*>(din + L.len), k.m, c.spkp, o,
-                     dout + O.status);
-  if ((rc = launch_check())) return rc;
-  ouro_tpraos_batch b{};
-  cbor::batch_from(&b, o, draw, k.m);
-  if (c.kind == kRawKes) {
-    rc = launch_kes(s.st, k.m, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig,
-                    dout + O.verdict);
+  const uint64_t* doff = reinterpret_cast<const uint64_t*>(din + L.off);
+  const uint32_t* dlen = reinterpret_cast<const uint32_t*>(din + L.len);
+  if (s.mode == kModeByron) {
+    // (a one-era chunk: status | verdict where the TPraos block has them)
+    if ((rc = raw_launch_byron(s, c, draw, k.bytes, doff, dlen, k.m, cbor::arena_base(darena),
+                               dout + O.status, dout + O.verdict)))
+      return rc;
   } else {
-    if (alphas) {
-      b.eta_alpha = din + L.alpha;
-      b.leader_alpha = din + L.alpha + 32 * k.m;
-    } else {
-      b.slot = dslot;
-      b.epoch_nonce = c.eta0 ? din + L.eta0 : nullptr;
-    }
-    if (c.nonce) b.eta_nonce = dout + O.nonce;
-    rc = launch_hdr(s.st, b, dout + O.verdict, dout + O.be, dout + O.bl);
+    if ((rc = raw_launch_tpraos(s, c, draw, k.bytes, doff, dlen, mt, cbor::arena_base(darena),
+                                dout, alphas ? din + L.alpha : nullptr,
+                                alphas ? din + L.alpha + 32 * k.m : nullptr,
+                                c.eta0 ? din + L.eta0 : nullptr,
+                                c.epochs ? din + L.tab : nullptr)))
+      return rc;
+    // a mixed chunk: its PBFT headers from the same uploaded bytes, through
+    // the tail of the lists, on the same stream
+    if (mb && (rc = raw_launch_byron(s, c, draw, k.bytes, doff + mt, dlen + mt, mb,
+                                     cbor::arena_base(darena + arena_t), dout + a16(O.total),
+                                     dout + a16(O.total) + OB.verdict)))
+      return rc;
   }
-  if (rc) return rc;
   OURO_HIP(hipMemcpyAsync(s.h_out, dout, back, hipMemcpyDeviceToHost, s.st));
+  if (back_b)
+    OURO_HIP(hipMemcpyAsync(s.h_out + a16(back), dout + a16(O.total), back_b,
+                            hipMemcpyDeviceToHost, s.st));
   OURO_HIP(hipEventRecord(s.done, s.st));
   s.lo = k.lo;
   s.m = k.m;
@@ -266,21 +360,55 @@ int raw_drain(RawSlot& s, const RawCall& c) {
   if (!s.busy) return OURO_OK;
   s.busy = false;
   OURO_HIP(hipEventSynchronize(s.done));
+  const bool hdr = c.kind == kRawHdr || c.kind == kRawChain;
+  if (s.mode == kModeMixed) {
+    // both result sets back to the caller's order (RawSlot idx: the TPraos
+    // rows' indices, then the PBFT rows')
+    const size_t mt = s.mt, mb = s.m - mt;
+    const RawOut O = raw_out(mt);
+    const RawOutB OB = raw_out_b(mb);
+    const uint8_t* h = s.h_out;
+    for (size_t j = 0; j < mt; j++) {
+      const size_t i = s.lo + s.idx[j];
+      const uint8_t st = h[O.status + j];
+      c.status[i] = st;
+      c.verdict[i] = st == OURO_PACK_OK ? h[O.verdict + j] : 0;
+      if (c.be) memcpy(c.be + 64 * i, h + O.be + 64 * j, 64);
+      if (c.bl) memcpy(c.bl + 64 * i, h + O.bl + 64 * j, 64);
+      if (c.nonce) memcpy(c.nonce + 32 * i, h + O.nonce + 32 * j, 32);
+    }
+    const uint8_t* hb = s.h_out + a16(raw_out_bytes(c, O, mt));
+    for (size_t j = 0; j < mb; j++) {
+      const size_t i = s.lo + s.idx[mt + j];
+      const uint8_t st = hb[OB.status + j];
+      c.status[i] = st;
+      c.verdict[i] = st == OURO_PACK_EBB ? 1 : (st == OURO_PACK_OK && hb[OB.verdict + j] ? 1 : 0);
+      if (c.be) memset(c.be + 64 * i, 0, 64);
+      if (c.bl) memset(c.bl + 64 * i, 0, 64);
+      if (c.nonce) memset(c.nonce + 32 * i, 0, 32);
+    }
+    return OURO_OK;
+  }
   const RawOut O = raw_out(s.m);
   const uint8_t* st = s.h_out + O.status;
   const uint8_t* v = s.h_out + O.verdict;
   memcpy(c.status + s.lo, st, s.m);
-  if (c.kind == kRawByron) {
+  if (s.mode == kModeByron) {
     // PBFT accepts an epoch-boundary header without a signature
     // (ouroboros-consensus/src/Ouroboros/Consensus/Protocol/PBFT.hs:327-328)
     for (size_t i = 0; i < s.m; i++)
       c.verdict[s.lo + i] = st[i] == OURO_PACK_EBB ? 1 : (st[i] == OURO_PACK_OK && v[i] ? 1 : 0);
+    if (hdr) {  // the combined entry: a PBFT header has no VRF outputs
+      if (c.be) memset(c.be + 64 * s.lo, 0, 64 * s.m);
+      if (c.bl) memset(c.bl + 64 * s.lo, 0, 64 * s.m);
+      if (c.nonce) memset(c.nonce + 32 * s.lo, 0, 32 * s.m);
+    }
     return OURO_OK;
   }
   // a header the slicer rejected is invalid (its zeroed row cannot verify;
   // masked so that no bit at all is set for it)
   for (size_t i = 0; i < s.m; i++) c.verdict[s.lo + i] = st[i] == OURO_PACK_OK ? v[i] : 0;
-  if (c.kind == kRawHdr) {
+  if (hdr) {
     if (c.be) memcpy(c.be + 64 * s.lo, s.h_out + O.be, 64 * s.m);
     if (c.bl) memcpy(c.bl + 64 * s.lo, s.h_out + O.bl, 64 * s.m);
     if (c.nonce) memcpy(c.nonce + 32 * s.lo, s.h_out + O.nonce, 32 * s.m);
@@ -301,7 +429,9 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
   // (profiles/r05a/cbor_sweep.jsonl); Byron's Ed25519 runs best with 5
   // (66.7--67.1 M headers/s against ~61 with 4 and 60--68 with 6, interleaved
   // on one box: profiles/r06k/byron_ab.jsonl)
-  const int S = (int)knob_size(ouro_knobs::get().cbor_slots, c.kind == kRawHdr ? 6 : (c.kind == kRawByron ? 5 : 4), 1,
+  // (the combined entry: the header kernel's count)
+  const bool hdr_kind = c.kind == kRawHdr || c.kind == kRawChain;
+  const int S = (int)knob_size(ouro_knobs::get().cbor_slots, hdr_kind ? 6 : (c.kind == kRawByron ? 5 : 4), 1,
                                 kRawMaxSlots);
   for (int k = 0; k < S; k++) {
     RawSlot& s = p.s[k];
@@ -361,8 +491,83 @@ int raw_host_byron(const RawCall& c) {
   return OURO_OK;
 }
 
+int raw_host(const RawCall& c);
+
+// The combined entry on the host path: per chunk of 64 K headers the same
+// partition as a mixed device chunk -- each class's offset / length (and
+// alpha) list through its own host slicer and verification, both result sets
+// scattered back to the caller's order.
+int raw_host_chain(const RawCall& c) {
+  const size_t C = 1 << 16;
+  std::vector<uint32_t> idx[2];
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  std::vector<uint8_t> st, v, be, bl, en, ea, la;
+  for (size_t lo = 0; lo < c.n; lo += C) {
+    const size_t m = std::min(C, c.n - lo);
+    idx[0].clear();
+    idx[1].clear();
+    for (size_t i = lo; i < lo + m; i++) {  // (every span was checked before any work)
+      c.proto[i] = (uint8_t)cbor::era_class(c.raw + c.off[i], c.len[i]);
+      idx[c.proto[i] == OURO_PROTO_TPRAOS ? 1 : 0].push_back((uint32_t)(i - lo));
+    }
+    for (int cls = 0; cls < 2; cls++) {
+      const std::vector<uint32_t>& ix = idx[cls];
+      const size_t q = ix.size();
+      if (!q) continue;
+      off.resize(q);
+      len.resize(q);
+      st.assign(q, 0);
+      v.assign(q, 0);
+      for (size_t j = 0; j < q; j++) {
+        off[j] = c.off[lo + ix[j]];
+        len[j] = c.len[lo + ix[j]];
+      }
+      RawCall sub{cls ? kRawHdr : kRawByron, c.raw, c.raw_bytes, off.data(), len.data(), q,
+                  c.spkp, nullptr, nullptr, nullptr, st.data(), v.data(), nullptr, nullptr,
+                  nullptr, c.magic};
+      if (cls) {
+        if (c.ea) {
+          ea.resize(32 * q);
+          la.resize(32 * q);
+          for (size_t j = 0; j < q; j++) {
+            memcpy(&ea[32 * j], c.ea + 32 * (lo + ix[j]), 32);
+            memcpy(&la[32 * j], c.la + 32 * (lo + ix[j]), 32);
+          }
+          sub.ea = ea.data();
+          sub.la = la.data();
+        }
+        sub.epochs = c.epochs;
+        sub.epochs_bytes = c.epochs_bytes;
+        if (c.be) be.assign(64 * q, 0), sub.be = be.data();
+        if (c.bl) bl.assign(64 * q, 0), sub.bl = bl.data();
+        if (c.nonce) en.assign(32 * q, 0), sub.nonce = en.data();
+      }
+      const int rc = raw_host(sub);
+      if (rc) return rc;
+      for (size_t j = 0; j < q; j++) {
+        const size_t i = lo + ix[j];
+        c.status[i] = st[j];
+        c.verdict[i] = v[j];
+        // (a PBFT header has no VRF outputs: zero rows)
+        if (c.be) cls ? memcpy(c.be + 64 * i, &be[64 * j], 64) : memset(c.be + 64 * i, 0, 64);
+        if (c.bl) cls ? memcpy(c.bl + 64 * i, &bl[64 * j], 64) : memset(c.bl + 64 * i, 0, 64);
+        if (c.nonce) cls ? memcpy(c.nonce + 32 * i, &en[32 * j], 32) : memset(c.nonce + 32 * i, 0, 32);
+      }
+    }
+  }
+  return OURO_OK;
+}
+
 int raw_host(const RawCall& c) {
   if (c.kind == kRawByron) return raw_host_byron(c);
+  if (c.kind == kRawChain) {
+    try {  // (its lists are vectors; no exception crosses the C ABI)
+      return raw_host_chain(c);
+    } catch (const std::bad_alloc&) {
+      return fail(OURO_EDEVICE, "raw CBOR host path: out of host memory");
+    }
+  }
   const size_t C = 1 << 16;
   const size_t cap = std::min(C, c.n);
   const size_t nb = ouro_tpraos_pack_bytes(cap);
@@ -388,7 +593,7 @@ int raw_host(const RawCall& c) {
       }
       if (c.nonce) b.eta_nonce = c.nonce + 32 * lo;
       rc = ouro_host::hdr_batch(&b, c.verdict + lo, c.be ? c.be + 64 * lo : nullptr,
-                                c.bl ? c.bl + 64 * lo : nullptr);
+                                c.bl ? c.bl + 64 * lo : nullptr, c.ea ? nullptr : c.epochs);
     }
     if (rc) return fail(rc, "raw CBOR host path failed");
     for (size_t i = lo; i < lo + m; i++)
@@ -399,15 +604,33 @@ int raw_host(const RawCall& c) {
 }  // namespace
 
 namespace ouro_rt {
-int raw_verify(const RawCall& c) {
-  if (c.n == 0) return OURO_OK;
+int raw_check(const RawCall& c) {
   if (!c.raw || !c.off || !c.len || !c.status || !c.verdict)
     return fail(OURO_EINVAL, "null argument");
+  if (c.kind == kRawChain && !c.proto) return fail(OURO_EINVAL, "null proto");
   if (c.kind != kRawByron && c.spkp == 0) return fail(OURO_EINVAL, "zero slots per KES period");
-  if (c.kind == kRawByron && (c.magic < -1 || c.magic > (int64_t)0xffffffffll))
+  if ((c.kind == kRawByron || c.kind == kRawChain) &&
+      (c.magic < -1 || c.magic > (int64_t)0xffffffffll))
     return fail(OURO_EINVAL, "protocol magic outside Word32 (or -1)");
   if ((c.ea == nullptr) != (c.la == nullptr))
     return fail(OURO_EINVAL, "give both VRF input arrays or neither");
+  if (c.ea && c.epochs)
+    return fail(OURO_EINVAL, "give an epoch schedule or the VRF input arrays, not both");
+  return OURO_OK;
+}
+
+int raw_verify_host(const RawCall& c) {
+  if (c.n == 0) return OURO_OK;
+  if (int rc = raw_check(c)) return rc;
+  for (size_t i = 0; i < c.n; i++)  // every span before any output is written
+    if (c.off[i] > c.raw_bytes || c.raw_bytes - c.off[i] < c.len[i])
+      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
+  return raw_host(c);
+}
+
+int raw_verify(const RawCall& c) {
+  if (c.n == 0) return OURO_OK;
+  if (int rc0 = raw_check(c)) return rc0;
   std::vector<RawChunk> chunks;
   const size_t per = knob_size(ouro_knobs::get().cbor_chunk, 65536, 256, (size_t)1 << 24);
   int rc = raw_chunks(c, per, &chunks);
@@ -463,6 +686,61 @@ int ouro_byron_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t*
   RawCall c{kRawByron, raw, raw_bytes, off, len, n, 0, nullptr, nullptr, nullptr, status,
             verdict, nullptr, nullptr, nullptr, protocol_magic};
   return raw_verify(c);
+}
+
+// A raw header stream across eras and epochs in one call (include/
+// ouro_verify.h): every header classified (cbor.h era_class) while the
+// pipeline gathers it, PBFT headers through the Byron slicer + ByronDSIGN
+// kernel, TPraos headers through the TPraos slicer + header kernel with mkSeed
+// under the epoch schedule, a mixed chunk through both on one upload.
+namespace {
+struct ChainArgs {
+  RawCall c;
+  std::vector<uint64_t> tab;
+};
+int chain_call(ChainArgs* a, const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+               const uint32_t* len, size_t n, uint64_t spkp, int64_t magic,
+               const ouro_epoch_nonces* epochs, const uint8_t* ea, const uint8_t* la,
+               uint8_t* proto, uint8_t* status, uint8_t* verdict, uint8_t* be, uint8_t* bl,
+               uint8_t* nonce) {
+  a->c = RawCall{kRawChain, raw, raw_bytes, off, len, n, spkp, nullptr, ea, la, status,
+                 verdict, be, bl, nonce, magic, proto};
+  if (n == 0) return OURO_OK;
+  if (epochs) {
+    if (int rc = epoch_tab_build(epochs, &a->tab)) return rc;
+    a->c.epochs = reinterpret_cast<const uint8_t*>(a->tab.data());
+    a->c.epochs_bytes = 8 * a->tab.size();
+  }
+  return raw_check(a->c);
+}
+}  // namespace
+
+int ouro_chain_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                           const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
+                           int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+                           const uint8_t* eta_alpha, const uint8_t* leader_alpha, uint8_t* proto,
+                           uint8_t* status, uint8_t* verdict, uint8_t* beta_eta,
+                           uint8_t* beta_leader, uint8_t* eta_nonce) {
+  ChainArgs a;
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  return raw_verify(a.c);
+}
+
+int ouro_chain_verify_cbor_host(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                                const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
+                                int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+                                const uint8_t* eta_alpha, const uint8_t* leader_alpha,
+                                uint8_t* proto, uint8_t* status, uint8_t* verdict,
+                                uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce) {
+  ChainArgs a;
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  return raw_verify_host(a.c);
 }
 
 // DIAGNOSTIC: the calling thread's last raw-CBOR call (ms and counts)

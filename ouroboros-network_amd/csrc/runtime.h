@@ -114,7 +114,14 @@ struct RawSlot {
   Buf d_in, d_arena, d_out;
   size_t lo = 0, m = 0;
   bool busy = false;
+  // the combined entry (kRawChain): the chunk's era make-up and, for a mixed
+  // chunk, its TPraos headers' indices (mt of them) followed by its PBFT
+  // headers' -- the order the per-class offset / length lists are in
+  int mode = 0;  // RawMode
+  size_t mt = 0;
+  std::vector<uint32_t> idx;
 };
+enum RawMode { kModeTpraos = 0, kModeByron = 1, kModeMixed = 2 };
 struct RawPipe {
   bool ready = false;
   RawSlot s[kRawMaxSlots];
@@ -238,7 +245,8 @@ int check_hdr_batch(const ouro_tpraos_batch* b);
 int stage_hdr(Stager& sg, const ouro_tpraos_batch* b, size_t lo, size_t m, StagedHdr* s);
 
 // ---- a raw-CBOR call (raw_pipe.cpp; multi.cpp shards one over devices) ----
-enum RawKind { kRawHdr = 0, kRawKes = 1, kRawByron = 2 };
+// (kRawChain: Byron and TPraos headers in one stream, classified per header)
+enum RawKind { kRawHdr = 0, kRawKes = 1, kRawByron = 2, kRawChain = 3 };
 struct RawCall {
   RawKind kind;
   const uint8_t* raw;
@@ -253,8 +261,19 @@ struct RawCall {
   uint8_t* verdict;
   uint8_t *be, *bl, *nonce;      // optional outputs (header kind)
   int64_t magic = -1;            // Byron: the configured ProtocolMagicId (-1: each header's)
+  uint8_t* proto = nullptr;      // chain kind: OUT, OURO_PROTO_* per header
+  // an epoch-nonce schedule block (epoch_tab_build), or null; header / chain kinds
+  const uint8_t* epochs = nullptr;
+  size_t epochs_bytes = 0;
 };
 int raw_verify(const RawCall& c);
+// the argument checks of a raw call that need no pass over the headers
+int raw_check(const RawCall& c);
+// the same call on the host path alone (ouro_chain_verify_cbor_host)
+int raw_verify_host(const RawCall& c);
+// an ouro_epoch_nonces checked (OURO_EINVAL) and packed as the block the lane
+// code reads (tpraos.h epoch_tab_*; api_batch.cpp)
+int epoch_tab_build(const ouro_epoch_nonces* e, std::vector<uint64_t>* tab);
 
 }  // namespace ouro_rt
 #pragma GCC visibility pop

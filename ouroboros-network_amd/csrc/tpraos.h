@@ -76,6 +76,11 @@ constexpr uint32_t kOptLeaderClaim = 2u;  // leader_output given
 constexpr uint32_t kOptSeeds = 4u;        // slot given: alphas = mkSeed on device
 constexpr uint32_t kOptEpochNonce = 8u;   // epoch_nonce given (else NeutralNonce)
 constexpr uint32_t kOptEtaNonce = 16u;    // eta_nonce output wanted
+// epoch_nonce points at an epoch-nonce schedule (EpochTab below) instead of
+// one eta0: the nonce is looked up per header by its slot.  Never taken from
+// the pointers (the public struct has no member for it): the epochs entries
+// pass it to the launch, which ORs it into the kernels' option word.
+constexpr uint32_t kOptEpochs = 32u;
 OURO_HD inline uint32_t batch_opts(const ouro_tpraos_batch& b) {
   return (b.eta_output ? kOptEtaClaim : 0u) | (b.leader_output ? kOptLeaderClaim : 0u) |
          (b.slot ? kOptSeeds : 0u) | (b.slot && b.epoch_nonce ? kOptEpochNonce : 0u) |
@@ -484,6 +489,29 @@ OURO_HD inline bool ocert_key_equal(const ouro_tpraos_batch& b, size_t i, size_t
   return ocert_key_equal_words(a, c);
 }
 
+// ---- the epoch-nonce schedule (include/ouro_verify.h ouro_epoch_nonces) -----
+// One block, 16-byte aligned, in host or device memory, built by the runtime
+// from the caller's validated schedule (epoch_tab_fill):
+//   word 0      k (1 .. OURO_EPOCHS_MAX), words 1..3 zero
+//   +16         first_slot[k] (uint64; strictly increasing, [0] == 0)
+//   +nonce_off  nonce[k][32]  (nonce_off = 16 + 8 (k rounded up to even))
+//   +neut_off   neutral[k]    (bytes; 1 = NeutralNonce)
+constexpr size_t epoch_tab_nonce_off(size_t k) { return 16 + 8 * ((k + 1) & ~(size_t)1); }
+constexpr size_t epoch_tab_neutral_off(size_t k) { return epoch_tab_nonce_off(k) + 32 * k; }
+constexpr size_t epoch_tab_bytes(size_t k) { return (epoch_tab_neutral_off(k) + k + 15) & ~(size_t)15; }
+// The entry of `slot`: the last j with first_slot[j] <= slot.  first_slot[0]
+// is 0, so there always is one; at most 12 steps for OURO_EPOCHS_MAX entries.
+OURO_FI uint32_t epoch_tab_find(const uint8_t* tab, uint64_t slot) {
+  const uint64_t* fs = reinterpret_cast<const uint64_t*>(tab + 16);
+  uint32_t lo = 0, hi = *reinterpret_cast<const uint32_t*>(tab);
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (fs[mid] <= slot) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
 // The VRF input of header i: mkSeed seedEta / seedL slot eta0 on the device
 // (Shelley/Protocol.hs:409-410; blake2b.h mkseed_hash) when the batch carries
 // slots, else the caller's 32 bytes.
@@ -491,8 +519,20 @@ OURO_HD inline bool ocert_key_equal(const ouro_tpraos_batch& b, size_t i, size_t
 OURO_NI void hdr_mkseed(uint32_t a[8], const ouro_tpraos_batch& b, size_t i, bool leader,
                         uint32_t opts) {
   uint32_t e0[8];
-  if (opts & kOptEpochNonce) ld_words(e0, b.epoch_nonce, 2);
-  mkseed_hash(a, b.slot[i], (opts & kOptEpochNonce) ? e0 : nullptr);
+  const uint64_t slot = b.slot[i];
+  bool have = (opts & kOptEpochNonce) != 0;
+  if (opts & kOptEpochs) {
+    // the header's epoch by its slot; neighbouring lanes are almost always in
+    // the same epoch, so these loads are mostly uniform
+    const uint8_t* tab = b.epoch_nonce;
+    const uint32_t k = *reinterpret_cast<const uint32_t*>(tab);
+    const uint32_t j = epoch_tab_find(tab, slot);
+    have = tab[epoch_tab_neutral_off(k) + j] == 0;
+    if (have) ld_words(e0, tab + epoch_tab_nonce_off(k) + 32 * (size_t)j, 2);
+  } else if (have) {
+    ld_words(e0, b.epoch_nonce, 2);
+  }
+  mkseed_hash(a, slot, have ? e0 : nullptr);
 #pragma unroll
   for (int k = 0; k < 8; k++) a[k] ^= leader ? kSeedL[k] : kSeedEta[k];
 }

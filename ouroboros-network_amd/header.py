@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .kes import periods_u32
-from .tpraos import HeaderBatch
+from .tpraos import EpochNonces, HeaderBatch
 
 
 class CBORError(ValueError):
@@ -105,6 +105,40 @@ def bytes_at(buf: bytes, i: int) -> bytes:
     if j + arg > len(buf):
         raise CBORError("truncated")
     return bytes(buf[j:j + arg])
+
+
+PROTO_PBFT, PROTO_TPRAOS = 0, 1
+
+
+def era_class(raw: bytes) -> int:
+    """The era of a raw header from its first few CBOR heads (csrc/cbor.h
+    era_class, the rule of ouro_chain_verify_cbor): PROTO_PBFT iff it is
+      * a definite array(2) whose first item is the definite uint 0 (HFC era 0),
+      * a definite array(2) whose first item is an array (Byron N2N v2), or
+      * #6.24 + a definite byte string whose payload starts with a definite
+        array(2) whose first item is a definite uint (Byron N2N v1);
+    PROTO_TPRAOS for everything else, truncated or unreadable input included
+    (the TPraos slicer's status then says why)."""
+    buf = bytes(raw)
+    try:
+        mt, arg, j = _head(buf, 0)
+        if mt == 4 and arg == 2:
+            mt1, a1, _ = _head(buf, j)
+            if mt1 == 0:
+                return PROTO_PBFT if a1 == 0 else PROTO_TPRAOS
+            return PROTO_PBFT if mt1 == 4 else PROTO_TPRAOS
+        if mt != 6 or arg != 24:
+            return PROTO_TPRAOS
+        mt, arg, j = _head(buf, j)
+        if mt != 2 or arg < 0:
+            return PROTO_TPRAOS
+        mt, arg, j = _head(buf, j)
+        if mt != 4 or arg != 2:
+            return PROTO_TPRAOS
+        mt1, a1, _ = _head(buf, j)
+        return PROTO_PBFT if mt1 == 0 and a1 >= 0 else PROTO_TPRAOS
+    except CBORError:
+        return PROTO_TPRAOS
 
 
 @dataclass
@@ -502,4 +536,55 @@ def verify_headers_cbor(raw_headers, slots_per_kes_period: int, *,
                                              ptr(status), ptr(verdict), ptr(be), ptr(bl), ptr(en))
             _native.check(rc, "ouro_tpraos_verify_cbor")
     out = (verdict[:n], be[:n], bl[:n], status[:n])
+    return out + (en[:n],) if nonce else out
+
+
+def verify_chain_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: int, *,
+                      epochs: Optional[EpochNonces] = None,
+                      eta_alpha: Optional[np.ndarray] = None,
+                      leader_alpha: Optional[np.ndarray] = None, nonce: bool = False,
+                      devices=None, host: bool = False):
+    """A raw header stream across eras and epochs in one call (include/
+    ouro_verify.h ouro_chain_verify_cbor): Byron and Shelley-family headers in
+    any order, each classified by era_class; PBFT rows as verify_byron_cbor
+    gives them (verdict 1 / 0, zero outputs), TPraos rows as
+    verify_headers_cbor does.  VRF inputs: both alpha arrays (n x 32, PBFT rows
+    ignored), else mkSeed under `epochs` (an EpochNonces; None = NeutralNonce
+    everywhere).  protocol_magic: the configured ProtocolMagicId, or -1 for
+    each Byron header's own.  host=True: the library's host path, no device;
+    devices (a list of indices, or "all"): ouro_chain_verify_cbor_multi.
+    Returns (proto, status, verdict, beta_eta, beta_leader[, eta_nonce])."""
+    import ctypes
+
+    from . import _native
+    buf, off, ln = raw_triplet(raw_headers)
+    n = int(off.size)
+    if ln.size != n:
+        raise ValueError("off / len: one entry per header")
+    m = max(n, 1)
+    proto = np.zeros(m, np.uint8)
+    status = np.zeros(m, np.uint8)
+    verdict = np.zeros(m, np.uint8)
+    be = np.zeros((m, 64), np.uint8)
+    bl = np.zeros((m, 64), np.uint8)
+    en = np.zeros((m, 32), np.uint8) if nonce else None
+    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    ea = None if eta_alpha is None else np.ascontiguousarray(eta_alpha, np.uint8).reshape(n, 32)
+    la = None if leader_alpha is None else \
+        np.ascontiguousarray(leader_alpha, np.uint8).reshape(n, 32)
+    e = None if epochs is None else ctypes.byref(epochs.c_struct())
+    if n:
+        lib = _native.load()
+        args = (ptr(buf), buf.size, ptr(off), ptr(ln), n, slots_per_kes_period, protocol_magic, e,
+                ptr(ea), ptr(la), ptr(proto), ptr(status), ptr(verdict), ptr(be), ptr(bl), ptr(en))
+        if host:
+            name, rc = "ouro_chain_verify_cbor_host", lib.ouro_chain_verify_cbor_host(*args)
+        elif devices is not None:
+            d, nd = _devices_arg(None if devices == "all" else devices)
+            name = "ouro_chain_verify_cbor_multi"
+            rc = lib.ouro_chain_verify_cbor_multi(ptr(d), nd, *args)
+        else:
+            name, rc = "ouro_chain_verify_cbor", lib.ouro_chain_verify_cbor(*args)
+        _native.check(rc, name)
+    out = (proto[:n], status[:n], verdict[:n], be[:n], bl[:n])
     return out + (en[:n],) if nonce else out

@@ -155,35 +155,102 @@ class HeaderBatch:
         return s
 
 
+@dataclass
+class EpochNonces:
+    """An epoch-nonce schedule (include/ouro_verify.h ouro_epoch_nonces):
+    entry j seeds the VRF inputs of first_slot[j] <= slot < first_slot[j + 1],
+    the last entry every slot from its first_slot up.  ``first_slot``: k
+    strictly increasing slots, the first one 0; ``nonce``: k x 32 bytes (eta0
+    of entry j); ``neutral``: k flags (1 = NeutralNonce, the row ignored) or
+    None.  The same rules as the C entries, checked here: ValueError."""
+
+    first_slot: np.ndarray
+    nonce: np.ndarray
+    neutral: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        fs = [int(x) for x in np.asarray(self.first_slot, dtype=object).ravel()]
+        k = len(fs)
+        if not 1 <= k <= _native.EPOCHS_MAX:
+            raise ValueError(f"epoch schedule: 1 .. {_native.EPOCHS_MAX} entries, got {k}")
+        if any(not 0 <= x < 1 << 64 for x in fs):
+            raise ValueError("epoch schedule: first_slot outside Word64")
+        if fs[0] != 0:
+            raise ValueError("epoch schedule: first_slot[0] must be 0")
+        if any(b <= a for a, b in zip(fs, fs[1:])):
+            raise ValueError("epoch schedule: first_slot must be strictly increasing")
+        if self.nonce is None:
+            raise ValueError("epoch schedule: nonce is required")
+        if isinstance(self.nonce, (list, tuple)):
+            self.nonce = np.frombuffer(b"".join(bytes(x) for x in self.nonce), np.uint8)
+        nonce = np.ascontiguousarray(self.nonce, np.uint8).reshape(-1)
+        if nonce.size != 32 * k:
+            raise ValueError("epoch schedule: nonce must be k x 32 bytes")
+        self.first_slot = np.array(fs, np.uint64)
+        self.nonce = nonce.reshape(k, 32)
+        if self.neutral is not None:
+            neutral = np.ascontiguousarray(self.neutral).reshape(-1)
+            if neutral.size != k:
+                raise ValueError("epoch schedule: one neutral flag per entry")
+            self.neutral = (neutral != 0).astype(np.uint8)
+
+    def __len__(self) -> int:
+        return int(self.first_slot.size)
+
+    def c_struct(self) -> _native.EpochNonces:
+        s = _native.EpochNonces()
+        s.k = len(self)
+        s.first_slot = ptr(self.first_slot)
+        s.nonce = ptr(self.nonce)
+        s.neutral = ptr(self.neutral) if self.neutral is not None else None
+        return s
+
+    def nonce_of(self, slot: int) -> Optional[bytes]:
+        """eta0 of `slot` (None = NeutralNonce): what the device looks up."""
+        j = int(np.searchsorted(self.first_slot, np.uint64(slot), side="right")) - 1
+        if self.neutral is not None and self.neutral[j]:
+            return None
+        return self.nonce[j].tobytes()
+
+
 def _outputs(n: int, nonce: bool):
     return (np.zeros(n, dtype=np.uint8), np.zeros((n, 64), dtype=np.uint8),
             np.zeros((n, 64), dtype=np.uint8), np.zeros((n, 32), np.uint8) if nonce else None)
 
 
-def verify_headers(batch: HeaderBatch, nonce: bool = False):
+def _verify(batch: HeaderBatch, nonce: bool, epochs: Optional[EpochNonces], name: str):
+    n = len(batch)
+    verdict, be, bl, en = _outputs(n, nonce)
+    if n:
+        s = batch.c_struct(en)
+        lib = _native.load()
+        if epochs is None:
+            rc = getattr(lib, name)(ctypes.byref(s), ptr(verdict), ptr(be), ptr(bl))
+        else:
+            name = name.replace("_batch", "_batch_epochs")
+            e = epochs.c_struct()
+            rc = getattr(lib, name)(ctypes.byref(s), ctypes.byref(e), ptr(verdict), ptr(be), ptr(bl))
+        _native.check(rc, name)
+    return (verdict, be, bl, en) if nonce else (verdict, be, bl)
+
+
+def verify_headers(batch: HeaderBatch, nonce: bool = False, *,
+                   epochs: Optional[EpochNonces] = None):
     """Verify every header; returns (verdict bits u8, beta_eta (n,64),
     beta_leader (n,64)), and with nonce=True also eta_nonce (n,32): the
-    mkNonceFromOutputVRF values the nonce fold consumes (nonce_fold)."""
-    n = len(batch)
-    verdict, be, bl, en = _outputs(n, nonce)
-    if n:
-        s = batch.c_struct(en)
-        rc = _native.load().ouro_tpraos_verify_batch(ctypes.byref(s), ptr(verdict), ptr(be), ptr(bl))
-        _native.check(rc, "ouro_tpraos_verify_batch")
-    return (verdict, be, bl, en) if nonce else (verdict, be, bl)
+    mkNonceFromOutputVRF values the nonce fold consumes (nonce_fold).
+    epochs (an EpochNonces): mkSeed's eta0 looked up per header by its slot
+    (ouro_tpraos_verify_batch_epochs), for a batch that spans epochs; the batch
+    then carries slots and neither epoch_nonce nor alphas."""
+    return _verify(batch, nonce, epochs, "ouro_tpraos_verify_batch")
 
 
-def verify_headers_host(batch: HeaderBatch, nonce: bool = False):
-    """verify_headers on the library's host path (ouro_tpraos_verify_batch_host:
-    the kernels' lane routines on the CPU threads); same results."""
-    n = len(batch)
-    verdict, be, bl, en = _outputs(n, nonce)
-    if n:
-        s = batch.c_struct(en)
-        rc = _native.load().ouro_tpraos_verify_batch_host(ctypes.byref(s), ptr(verdict), ptr(be),
-                                                          ptr(bl))
-        _native.check(rc, "ouro_tpraos_verify_batch_host")
-    return (verdict, be, bl, en) if nonce else (verdict, be, bl)
+def verify_headers_host(batch: HeaderBatch, nonce: bool = False, *,
+                        epochs: Optional[EpochNonces] = None):
+    """verify_headers on the library's host path (ouro_tpraos_verify_batch_host
+    / _epochs_host: the kernels' lane routines on the CPU threads); same
+    results."""
+    return _verify(batch, nonce, epochs, "ouro_tpraos_verify_batch_host")
 
 
 def nonce_fold(eta_nonce: np.ndarray, slot: np.ndarray, first_slot_next_epoch: int,
