@@ -423,6 +423,98 @@ int ouro_integrity_verify_cbor_device(void *stream, const uint8_t *raw, size_t r
                                       uint64_t slots_per_kes_period, void *arena,
                                       size_t arena_bytes, uint8_t *status, uint8_t *verdict);
 
+/* Batched Blake2b-256 (RFC 7693, unkeyed, 32-byte digest) over arbitrary
+ * spans: out[i] = Blake2b-256(msg[off[i] .. off[i] + len[i])), spans of any
+ * length up to 2^32 - 1, any byte alignment, overlapping or identical spans
+ * allowed.  The hash of the reference's HASH Blake2b_256: the block body hash
+ * below (ledger-specs bbHash behind blockMatchesHeader,
+ * ouroboros-consensus-shelley/src/Ouroboros/Consensus/Shelley/Ledger/Block.hs:127-130),
+ * and header / prev hashes (ShelleyHash, .../Shelley/Ledger/Block.hs:63).
+ * One lane per message on the device, the messages ordered by length class
+ * (the bit length of their compression count) so that a wave's lanes run
+ * alike; OURO_BLOCK_SORT=0 turns the ordering off (A/B).
+ *   ouro_blake2b256_batch: host buffers; one upload, launch and copy-back on
+ *     the calling thread's stream, synchronous; a device error recomputes on
+ *     the host path.
+ *   ouro_blake2b256_batch_host: the host path alone (the same lane routine
+ *     compiled for the host, split over the worker pool).
+ *   Both return OURO_EINVAL, before any work, for NULLs or a span outside
+ *   msg_bytes.
+ *   ouro_blake2b256_batch_device: device pointers, enqueued on `stream`, not
+ *     synchronised.  A lane reads the aligned dwords its span touches and
+ *     no other, so msg must be 4-byte aligned and its allocation must extend
+ *     to the next multiple of 4 above msg_bytes (the dword holding the last
+ *     byte is read whole; hipMalloc'd buffers always do).  out must be
+ *     16-byte aligned; work: ouro_blake2b256_work_bytes(n) bytes of device
+ *     memory.  A
+ *     span outside msg_bytes is not read; its digest is 32 zero bytes. */
+int ouro_blake2b256_batch(size_t n, const uint8_t *msg, size_t msg_bytes, const uint64_t *off,
+                          const uint32_t *len, uint8_t *out);
+int ouro_blake2b256_batch_host(size_t n, const uint8_t *msg, size_t msg_bytes,
+                               const uint64_t *off, const uint32_t *len, uint8_t *out);
+size_t ouro_blake2b256_work_bytes(size_t n);
+int ouro_blake2b256_batch_device(void *stream, size_t n, const uint8_t *msg, size_t msg_bytes,
+                                 const uint64_t *off, const uint32_t *len, uint8_t *out,
+                                 void *work, size_t work_bytes);
+
+/* Whole-block storage integrity straight from raw block CBOR: replaces
+ * verifyBlockIntegrity (ouroboros-consensus-shelley/src/Ouroboros/Consensus/
+ * Shelley/Ledger/Integrity.hs:45-51) = verifyHeaderIntegrity hdr &&
+ * blockMatchesHeader hdr blk, as the storage layer runs it on every block --
+ * the VolatileDB parser (ouroboros-consensus/src/Ouroboros/Consensus/Storage/
+ * VolatileDB/Impl/Parser.hs:66-85), ImmutableDB chunk validation
+ * (.../ImmutableDB/Impl/Validation.hs:358-365) and GetVerifiedBlock -- and
+ * blockMatchesHeader alone as the BlockFetch client runs it on every block it
+ * downloads (ouroboros-network/src/Ouroboros/Network/BlockFetch/Client.hs:280).
+ * Block i is raw[off[i] .. off[i] + len[i]) in any of the forms
+ *   [header, txBodies, txWitnesses, txMetadata]             Shelley on disk
+ *   #6.24(bytes .cbor block)                                Shelley on the wire
+ *   [tag, block]                                            Cardano on disk
+ *   #6.24(bytes .cbor [tag, block])                         Cardano on the wire
+ * with header = [header_body, kes_sig] (plain, not tag-24 wrapped).  The HFC
+ * block tag is 0 = Byron EBB, 1 = Byron regular (both status OURO_PACK_EBYRON:
+ * Byron's body proof is out of scope), 2 and up = Shelley family.  The block
+ * must be a definite array(4) that ends exactly where its span (the tag-24
+ * payload) ends.  blockMatchesHeader (.../Shelley/Ledger/Block.hs:127-130):
+ *   bbHash = Blake2b-256(Blake2b-256(txBodies) || Blake2b-256(txWitnesses)
+ *                        || Blake2b-256(txMetadata))  ==  header_body field 8
+ * each inner hash over the item's bytes exactly as they stand in the block.
+ * Outputs: status[i] = OURO_PACK_*; verdict[i] = OURO_BLK_* bits, 0 for a
+ * block that does not slice; body_hash (n x 32, may be NULL) the computed
+ * bbHash, zeros for a block that does not slice.
+ *   ouro_block_integrity_verify_cbor: host buffers (pageable is fine),
+ *     synchronous, on the raw-CBOR pipeline described at
+ *     ouro_tpraos_verify_cbor: chunks of whole blocks gathered into pinned
+ *     staging, uploaded once; slicer, segment hashes, Sum6KES and finish on
+ *     the slot's stream; 4 chunks in flight; a device error recomputes the
+ *     batch on the host path.
+ *   ouro_block_integrity_verify_cbor_host: the host path alone.
+ *   Both return OURO_EINVAL, before any work, for a span outside raw_bytes,
+ *   NULLs or a zero period.
+ *   ouro_block_integrity_verify_cbor_device: device pointers (raw 4-byte
+ *     aligned and allocated up to the next multiple of 4 above raw_bytes,
+ *     see ouro_blake2b256_batch_device; arena of
+ *     ouro_block_pack_bytes(n) bytes), enqueued on `stream`, not synchronised;
+ *     a span outside raw_bytes is per-block status OURO_PACK_ESPAN.
+ * Out of scope: _multi forms, Byron blocks, the latency plans. */
+#define OURO_BLK_KES_OK 0x01u  /* verifyHeaderIntegrity                       */
+#define OURO_BLK_BODY_OK 0x02u /* blockMatchesHeader: bbHash == bodyHash      */
+#define OURO_BLK_ALL_OK 0x03u  /* verifyBlockIntegrity; test with the mask    */
+size_t ouro_block_pack_bytes(size_t n);
+int ouro_block_integrity_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                     const uint32_t *len, size_t n,
+                                     uint64_t slots_per_kes_period, uint8_t *status,
+                                     uint8_t *verdict, uint8_t *body_hash);
+int ouro_block_integrity_verify_cbor_host(const uint8_t *raw, size_t raw_bytes,
+                                          const uint64_t *off, const uint32_t *len, size_t n,
+                                          uint64_t slots_per_kes_period, uint8_t *status,
+                                          uint8_t *verdict, uint8_t *body_hash);
+int ouro_block_integrity_verify_cbor_device(void *stream, const uint8_t *raw, size_t raw_bytes,
+                                            const uint64_t *off, const uint32_t *len, size_t n,
+                                            uint64_t slots_per_kes_period, void *arena,
+                                            size_t arena_bytes, uint8_t *status, uint8_t *verdict,
+                                            uint8_t *body_hash);
+
 /* Raw Byron header CBOR -> the inputs of its PBFT block-signature check
  * (SURVEY.md §8(f) row 4).  Replaces the per-header decode + message assembly
  * in front of ByronDSIGN.verifyDSIGN: Byron/Ledger/PBFT.hs:47-73 builds

@@ -22,7 +22,7 @@ int ouro_debug_host_path(unsigned long long *single_items,
                          unsigned long long *recomputed_batches);
 
 /* Re-read the library's environment switches (OURO_SINGLE_ITEM,
- * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_HOST_*, OURO_CBOR_*,
+ * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_BLOCK_SORT, OURO_HOST_*, OURO_CBOR_*,
  * OURO_LAT_*, OURO_PLAN_*; csrc/knobs.h).  The library reads them once, on
  * first use, and never on a call path: a process that changes one (tests,
  * bench.py A/B passes) calls this afterwards.  Plans keep the values they

@@ -8,6 +8,7 @@ is the gfx950 library ``lib/libouro_verify.so`` behind the C ABI in
 """
 from . import _native
 from ._native import DeviceError, NativeUnavailable
+from .block import blake2b256_batch, parse_block, verify_block_integrity_cbor
 from .byron import (ByronDSIGN, dlg_cert_message, pack_byron_cbor, parse_byron_header,
                     verify_byron_cbor, verify_byron_headers, verify_delegation_certs)
 from .dsign import Ed25519DSIGN
@@ -25,11 +26,14 @@ __all__ = [
     "NativeUnavailable",
     "PraosVRF",
     "Sum6KES",
+    "blake2b256_batch",
     "first_invalid",
     "kes_period",
     "dlg_cert_message",
     "pack_byron_cbor",
+    "parse_block",
     "parse_byron_header",
+    "verify_block_integrity_cbor",
     "verify_byron_cbor",
     "verify_byron_headers",
     "verify_chain_cbor",

@@ -35,6 +35,10 @@ HDR_LEADER_S_UNREDUCED = 0x80
 HDR_S_UNREDUCED = 0xC0
 VRF_STRICT_S = 0x1             # ouro_vrf03_verify_batch_flags: reject s >= L
 
+BLK_KES_OK = 0x01      # ouro_block_integrity_verify_cbor: verifyHeaderIntegrity
+BLK_BODY_OK = 0x02     # blockMatchesHeader
+BLK_ALL_OK = 0x03      # verifyBlockIntegrity
+
 PROTO_PBFT = 0     # ouro_chain_verify_cbor proto[i]: a Byron header
 PROTO_TPRAOS = 1   # a Shelley-family header (and anything unreadable)
 EPOCHS_MAX = 4096  # OURO_EPOCHS_MAX
@@ -162,6 +166,16 @@ SIGNATURES = {
     "ouro_debug_reload_knobs": (None, []),
     "ouro_integrity_verify_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, ctypes.c_uint64, _P,
                                                _SZ, _P, _P]),
+    "ouro_blake2b256_batch": (_I, [_SZ, _P, _SZ, _P, _P, _P]),
+    "ouro_blake2b256_batch_host": (_I, [_SZ, _P, _SZ, _P, _P, _P]),
+    "ouro_blake2b256_work_bytes": (_SZ, [_SZ]),
+    "ouro_blake2b256_batch_device": (_I, [_P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ]),
+    "ouro_block_pack_bytes": (_SZ, [_SZ]),
+    "ouro_block_integrity_verify_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, _P, _P, _P]),
+    "ouro_block_integrity_verify_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, _P, _P,
+                                                   _P]),
+    "ouro_block_integrity_verify_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
+                                                     _P, _SZ, _P, _P, _P]),
     "ouro_sum6kes_verify_batch": (_I, [_SZ, _P, _P, _P, _P, _P, _P, _P]),
     "ouro_tpraos_verify_batch": (_I, [ctypes.POINTER(TPraosBatch), _P, _P, _P]),
     "ouro_ed25519_verify_batch_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blake2b_stream.h"
 #include "leader.h"
 #include "tpraos.h"
 
@@ -178,6 +179,63 @@ void dh_blake2b256_64(uint8_t* out, const uint8_t* in64) {
   for (int i = 0; i < 16; i++) w[i] = ld_le32(in64 + 4 * i);
   blake2b256_64(h, w);
   memcpy(out, h, 32);
+}
+// the streaming Blake2b-256 (blake2b_stream.h): the host build's memcpy loads
+void dh_blake2b256_stream(uint8_t* out, const uint8_t* msg, uint32_t len) {
+  uint32_t h[8];
+  blake2b256_stream(h, msg, len);
+  memcpy(out, h, 32);
+}
+void dh_blake2b256_96(uint8_t* out, const uint8_t* in96) {
+  uint32_t w[24], h[8];
+  for (int i = 0; i < 24; i++) w[i] = ld_le32(in96 + 4 * i);
+  blake2b256_96(h, w);
+  memcpy(out, h, 32);
+}
+// ... and the same hash through the DEVICE's block loads (b2b_load_dwords:
+// aligned dwords funnel-shifted by the span's misalignment) with a loader
+// that checks the load rule: every dword read is aligned and holds at least
+// one byte of the span msg[0 .. len).  Returns the number of dwords read, or
+// -1 on the first read that breaks the rule.
+int dh_blake2b256_dwords(uint8_t* out, const uint8_t* msg, uint32_t len) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(msg), e0 = a0 + len;
+  int loads = 0;
+  bool bad = false;
+  auto ld = [&](uintptr_t x) -> uint32_t {
+    if ((x & 3) || len == 0 || x + 4 <= a0 || x >= e0) {
+      bad = true;
+      return 0xdeadbeefu;
+    }
+    loads++;
+    // (only the bytes of the span are the caller's: the rest of the dword
+    // comes back as set bits, which the routine must shift or mask away)
+    uint32_t v = 0;
+    for (int k = 0; k < 4; k++) {
+      const uintptr_t b = x + (uintptr_t)k;
+      const uint32_t byte = (b >= a0 && b < e0) ? *reinterpret_cast<const uint8_t*>(b) : 0xffu;
+      v |= byte << (8 * k);
+    }
+    return v;
+  };
+  uint64_t h[8];
+  for (int i = 0; i < 8; i++) h[i] = kB2bIV[i];
+  h[0] ^= 0x01010000ULL ^ 32;
+  uintptr_t p = a0;
+  uint32_t left = len;
+  uint64_t t = 0;
+  for (;;) {
+    const bool last = left <= 128;
+    const uint32_t take = last ? left : 128u;
+    uint64_t m[16];
+    b2b_load_dwords(m, p, take, ld);
+    t += take;
+    b2b_compress(h, m, t, last);
+    if (last) break;
+    p += take;
+    left -= take;
+  }
+  memcpy(out, h, 32);
+  return bad ? -1 : loads;
 }
 void dh_elligator2(uint8_t* out, const uint8_t* r32) {
   uint32_t r[8];

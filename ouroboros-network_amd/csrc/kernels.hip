@@ -25,6 +25,8 @@
 
 #include "../../include/ouro_verify.h"
 #include "cbor.h"
+#include "blake2b_stream.h"
+#include "cbor_block.h"
 #include "cbor_byron.h"
 #include "host_path.h"
 #include "knobs.h"
@@ -531,6 +533,165 @@ __global__ void __launch_bounds__(kBlock) k_byron_pack(const uint8_t* __restrict
   }
 }
 
+// ---- whole-block storage integrity (cbor_block.h) ----
+// The block slicer on the device, one lane per block: the TPraos header rows
+// of item 0 (the KES kernel's inputs), the claimed bodyHash and the spans of
+// items 1..3.  A rejected block's rows are zeroed (its three spans are then
+// empty: the hash kernel reads nothing for them).
+__global__ void __launch_bounds__(kBlock) k_block_pack(const uint8_t* __restrict__ raw,
+                                                       size_t raw_bytes,
+                                                       const uint64_t* __restrict__ off,
+                                                       const uint32_t* __restrict__ len, size_t n,
+                                                       uint64_t spkp, cbor::Out o, cbor::BlockOut bo,
+                                                       uint8_t* __restrict__ status) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n; i += nth) {
+    const uint64_t o0 = off[i];
+    const uint32_t l0 = len[i];
+    uint8_t st = (o0 > raw_bytes || raw_bytes - o0 < l0)
+                     ? (uint8_t)OURO_PACK_ESPAN
+                     : cbor::block_one(raw, o0, l0, spkp, o, bo, i);
+    if (st != OURO_PACK_OK) cbor::block_zero_row(o, bo, i);
+    status[i] = st;
+  }
+}
+
+// The length class of a message: the bit length of its compression count
+// (1 for up to 128 bytes, the empty message included; at most 26).
+__device__ __forceinline__ uint32_t b2b_class(uint32_t len) {
+  const uint32_t nc = len ? (len >> 7) + ((len & 127u) ? 1u : 0u) : 1u;
+  return 32u - (uint32_t)__clz((int)nc);
+}
+// the sort's 64 counters cleared on the stream (a kernel, not a memset: no
+// host-side wait on a stream that other chunks' work shares the device with)
+__global__ void k_b2b_clear(uint32_t* cnt) {
+  if (blockIdx.x == 0 && threadIdx.x < 64) cnt[threadIdx.x] = 0;
+}
+// The counting sort of the work items by length class, so that the 64 lanes
+// of a wave hash spans of similar length (a wave runs as long as its longest
+// lane): counts per class (cnt[0..31], cleared by k_b2b_clear), ...
+__global__ void __launch_bounds__(kBlock) k_b2b_count(size_t m, const uint32_t* __restrict__ len,
+                                                      uint32_t* cnt) {
+  __shared__ uint32_t s_cnt[32];
+  if (threadIdx.x < 32) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < m; i += nth) atomicAdd(&s_cnt[b2b_class(len[i])], 1u);
+  __syncthreads();
+  if (threadIdx.x < 32 && s_cnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], s_cnt[threadIdx.x]);
+}
+// ... each class's first position, the longest class first (start[c] =
+// cnt[32 + c]; one thread: 32 counters), ...
+__global__ void k_b2b_starts(uint32_t* cnt) {
+  if (blockIdx.x || threadIdx.x) return;
+  uint32_t at = 0;
+  for (int c = 31; c >= 0; c--) {
+    cnt[32 + c] = at;
+    at += cnt[c];
+  }
+}
+// ... and the permutation: lane j of the hash kernel takes item perm[j].  A
+// workgroup ranks its 256 items per class in LDS and reserves each class's
+// range with ONE global atomic, so a batch of one class does not serialise
+// on a single counter, and neighbouring items stay neighbours inside a class
+// (the three segments of a block are adjacent in memory).
+__global__ void __launch_bounds__(kBlock) k_b2b_scatter(size_t m, const uint32_t* __restrict__ len,
+                                                        uint32_t* cnt, uint32_t* __restrict__ perm) {
+  __shared__ uint32_t s_cnt[32], s_base[32];
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  // (whole workgroups: every thread reaches the barriers)
+  for (size_t base = (size_t)blockIdx.x * blockDim.x; base < m; base += nth) {
+    const size_t i = base + threadIdx.x;
+    if (threadIdx.x < 32) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t c = 0, rank = 0;
+    if (i < m) {
+      c = b2b_class(len[i]);
+      rank = atomicAdd(&s_cnt[c], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && s_cnt[threadIdx.x])
+      s_base[threadIdx.x] = atomicAdd(&cnt[32 + threadIdx.x], s_cnt[threadIdx.x]);
+    __syncthreads();
+    if (i < m) {
+      const size_t pos = (size_t)s_base[c] + rank;
+      if (pos < m) perm[pos] = (uint32_t)i;  // (pos < m always: the counts sum to m)
+    }
+    __syncthreads();
+  }
+}
+
+// Workgroups of one wave: in sorted order the long messages fill the first
+// waves, and single-wave workgroups spread those over the CUs instead of
+// packing four of them onto one.
+constexpr int kB2bBlock = 64;
+// out[i] = Blake2b-256(msg[off[i] .. off[i] + len[i])), one lane per message
+// (blake2b_stream.h), item perm[j] on lane j (perm null: item j).  msg must
+// be 4-byte aligned: the lane reads the aligned dwords its span touches.  A
+// span outside msg_bytes is not read; its digest is zero.
+__global__ void __launch_bounds__(kB2bBlock) k_blake2b256(size_t m, const uint8_t* __restrict__ msg,
+                                                       size_t msg_bytes,
+                                                       const uint64_t* __restrict__ off,
+                                                       const uint32_t* __restrict__ len,
+                                                       const uint32_t* __restrict__ perm,
+                                                       uint8_t* __restrict__ out) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t j = tid; j < m; j += nth) {
+    const size_t i = perm ? (size_t)perm[j] : j;
+    if (i >= m) continue;
+    const uint64_t o0 = off[i];
+    const uint32_t l0 = len[i];
+    uint32_t d[8];
+    if (o0 > msg_bytes || msg_bytes - o0 < l0) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) d[k] = 0;
+    } else {
+      blake2b256_stream(d, msg + o0, l0);
+    }
+    stg4(out + 32 * i, make_int4((int)d[0], (int)d[1], (int)d[2], (int)d[3]));
+    stg4(out + 32 * i + 16, make_int4((int)d[4], (int)d[5], (int)d[6], (int)d[7]));
+  }
+}
+
+// bbHash = Blake2b-256 of the block's three segment digests (96 bytes: one
+// final compression with t = 96), compared with the claimed bodyHash and
+// merged with the KES verdict: verdict[i] = OURO_BLK_* bits, 0 (and a zero
+// body_hash) for a block that did not slice.  body_hash may be null.
+__global__ void __launch_bounds__(kBlock) k_block_finish(size_t n, const uint8_t* __restrict__ status,
+                                                         const uint8_t* __restrict__ digest,
+                                                         const uint8_t* __restrict__ claimed,
+                                                         const uint8_t* __restrict__ kes,
+                                                         uint8_t* __restrict__ verdict,
+                                                         uint8_t* __restrict__ body_hash) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n; i += nth) {
+    uint32_t h[8];
+    uint8_t v = 0;
+    if (status[i] == OURO_PACK_OK) {
+      uint32_t in[24], c[8];
+      load_words(in, digest + 96 * i, 6);
+      load_words(c, claimed + 32 * i, 2);
+      blake2b256_96(h, in);
+      uint32_t diff = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) diff |= h[k] ^ c[k];
+      v = (uint8_t)((kes[i] ? OURO_BLK_KES_OK : 0u) | (diff == 0 ? OURO_BLK_BODY_OK : 0u));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; k++) h[k] = 0;
+    }
+    verdict[i] = v;
+    if (body_hash) {
+      // (the caller's buffer: n x 32 at any alignment)
+      for (int k = 0; k < 32; k++) body_hash[32 * i + k] = (uint8_t)(h[k >> 2] >> (8 * (k & 3)));
+    }
+  }
+}
+
 // leader threshold (leader.h), one item per lane; verdict 1 / 0 / 0xff
 __global__ void __launch_bounds__(kBlock) k_leader_check(size_t n, const uint8_t* __restrict__ beta,
                                                          const uint64_t* __restrict__ num,
@@ -926,6 +1087,43 @@ void launch_plan_stage(hipStream_t st, unsigned blocks, const uint4* src, uint4*
 void launch_plan_stage_ranges(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst,
                               const PlanRanges& r, uint64_t* stamp) {
   hipLaunchKernelGGL(k_plan_stage_ranges, dim3(blocks), dim3(256), 0, st, src, dst, r, stamp);
+}
+
+// ---- whole-block storage integrity ----
+void launch_block_pack(hipStream_t st, unsigned blocks, const uint8_t* raw, size_t raw_bytes,
+                       const uint64_t* off, const uint32_t* len, size_t n, uint64_t spkp,
+                       const cbor::Out& o, const cbor::BlockOut& bo, uint8_t* status) {
+  hipLaunchKernelGGL(k_block_pack, dim3(blocks), dim3(kBlock), 0, st, raw, raw_bytes, off, len, n,
+                     spkp, o, bo, status);
+}
+// m messages hashed on `st`; work: cbor::b2b_work_bytes(m) bytes of device
+// memory, 64-byte aligned (the permutation and its class counters).
+// OURO_BLOCK_SORT=0: no ordering, lane j hashes item j (A/B).
+int launch_blake2b(hipStream_t st, size_t m, const uint8_t* msg, size_t msg_bytes,
+                   const uint64_t* off, const uint32_t* len, uint8_t* out, void* work) {
+  if (m == 0) return OURO_OK;
+  if (m > 0xffffffffull) return fail(OURO_EINVAL, "more than 2^32 - 1 messages");
+  const unsigned blocks = (unsigned)std::min<size_t>((m + kBlock - 1) / kBlock, 4096);
+  const uint32_t* perm = nullptr;
+  if (ouro_knobs::get().block_sort.load(std::memory_order_relaxed) != 0) {
+    uint32_t* p = static_cast<uint32_t*>(work);
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(work) + cbor::a64(4 * m));
+    hipLaunchKernelGGL(k_b2b_clear, dim3(1), dim3(64), 0, st, cnt);
+    hipLaunchKernelGGL(k_b2b_count, dim3(blocks), dim3(kBlock), 0, st, m, len, cnt);
+    hipLaunchKernelGGL(k_b2b_starts, dim3(1), dim3(64), 0, st, cnt);
+    hipLaunchKernelGGL(k_b2b_scatter, dim3(blocks), dim3(kBlock), 0, st, m, len, cnt, p);
+    perm = p;
+  }
+  const unsigned hblocks = (unsigned)std::min<size_t>((m + kB2bBlock - 1) / kB2bBlock, 1u << 20);
+  hipLaunchKernelGGL(k_blake2b256, dim3(hblocks), dim3(kB2bBlock), 0, st, m, msg, msg_bytes, off,
+                     len, perm, out);
+  return launch_check();
+}
+void launch_block_finish(hipStream_t st, unsigned blocks, size_t n, const uint8_t* status,
+                         const uint8_t* digest, const uint8_t* claimed, const uint8_t* kes,
+                         uint8_t* verdict, uint8_t* body_hash) {
+  hipLaunchKernelGGL(k_block_finish, dim3(blocks), dim3(kBlock), 0, st, n, status, digest, claimed,
+                     kes, verdict, body_hash);
 }
 
 }  // namespace ouro_rt

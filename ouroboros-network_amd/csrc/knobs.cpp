@@ -42,6 +42,7 @@ void load(Knobs& k) {
   read_size<size_t>(k.cbor_slots, "OURO_CBOR_SLOTS", 0);
   read_size<size_t>(k.cbor_copy_threads, "OURO_CBOR_COPY_THREADS", 0);
   read_int(k.cbor_ramp, "OURO_CBOR_RAMP", 0);
+  read_int(k.block_sort, "OURO_BLOCK_SORT", 1);
   read_int(k.lat_block, "OURO_LAT_BLOCK", 0);
   read_int(k.lat_quad, "OURO_LAT_QUAD", 1);
   read_int(k.lat_wide, "OURO_LAT_WIDE", 0xff);

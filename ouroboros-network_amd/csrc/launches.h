@@ -7,6 +7,7 @@
 
 #include "../../include/ouro_verify.h"
 #include "cbor.h"
+#include "cbor_block.h"
 #include "cbor_byron.h"
 
 // the byte ranges of a plan window's copy kernel (kernels.hip
@@ -77,6 +78,17 @@ void launch_tpraos_pack(hipStream_t st, unsigned blocks, const uint8_t* raw, siz
 void launch_byron_pack(hipStream_t st, unsigned blocks, const uint8_t* raw, size_t raw_bytes,
                        const uint64_t* off, const uint32_t* len, size_t n, int64_t magic,
                        const ouro::cbor::ByronOut& o, uint8_t* status);
+// whole-block storage integrity (cbor_block.h): the block slicer, the batched
+// Blake2b-256 (work: cbor::b2b_work_bytes(m) bytes of device memory, 64-byte
+// aligned; checks its own launches) and the body-hash finish
+void launch_block_pack(hipStream_t st, unsigned blocks, const uint8_t* raw, size_t raw_bytes,
+                       const uint64_t* off, const uint32_t* len, size_t n, uint64_t spkp,
+                       const ouro::cbor::Out& o, const ouro::cbor::BlockOut& bo, uint8_t* status);
+int launch_blake2b(hipStream_t st, size_t m, const uint8_t* msg, size_t msg_bytes,
+                   const uint64_t* off, const uint32_t* len, uint8_t* out, void* work);
+void launch_block_finish(hipStream_t st, unsigned blocks, size_t n, const uint8_t* status,
+                         const uint8_t* digest, const uint8_t* claimed, const uint8_t* kes,
+                         uint8_t* verdict, uint8_t* body_hash);
 void launch_vrf03_proof_to_hash(hipStream_t st, unsigned blocks, size_t n, const uint8_t* proof,
                                 uint8_t* beta, uint8_t* verdict);
 void launch_plan_stage(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst, size_t n16,

@@ -104,6 +104,8 @@ RawOut raw_out(size_t m) {
 }
 // bytes of the result block copied back
 size_t raw_out_bytes(const RawCall& c, const RawOut& o, size_t m) {
+  // (the block kind: its body hashes, 32 B each, where beta_eta would start)
+  if (c.kind == kRawBlock) return c.body_hash ? o.be + 32 * m : o.verdict + m;
   if (c.kind != kRawHdr && c.kind != kRawChain) return o.verdict + m;
   if (c.nonce) return o.slot;
   if (c.bl) return o.nonce;
@@ -310,7 +312,9 @@ int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
   // bytes copied back: one era's block, or a mixed chunk's two
   const size_t back = mt ? raw_out_bytes(c, O, mt) : O.verdict + k.m;
   const size_t back_b = s.mode == kModeMixed ? OB.verdict + mb : 0;
-  const size_t arena_t = mt ? a16(ouro_tpraos_pack_bytes(mt)) + 64 : 0;
+  const size_t arena_t = !mt ? 0
+                         : c.kind == kRawBlock ? a16(ouro_block_pack_bytes(mt)) + 64
+                                               : a16(ouro_tpraos_pack_bytes(mt)) + 64;
   const cbor::ByronLayout bl = cbor::byron_layout(mb, k.bytes + cbor::kByronMsgExtra * mb);
   int rc;
   if ((rc = ensure(s.d_in, L.total)) ||
@@ -329,6 +333,12 @@ int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
     // (a one-era chunk: status | verdict where the TPraos block has them)
     if ((rc = raw_launch_byron(s, c, draw, k.bytes, doff, dlen, k.m, cbor::arena_base(darena),
                                dout + O.status, dout + O.verdict)))
+      return rc;
+  } else if (c.kind == kRawBlock) {
+    // whole blocks: slicer, segment hashes, Sum6KES and the finish (block_api.cpp)
+    if ((rc = block_launch(s.st, draw, k.bytes, doff, dlen, mt, c.spkp, cbor::arena_base(darena),
+                           dout + O.status, dout + O.verdict,
+                           c.body_hash ? dout + O.be : nullptr)))
       return rc;
   } else {
     if ((rc = raw_launch_tpraos(s, c, draw, k.bytes, doff, dlen, mt, cbor::arena_base(darena),
@@ -408,6 +418,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
   // a header the slicer rejected is invalid (its zeroed row cannot verify;
   // masked so that no bit at all is set for it)
   for (size_t i = 0; i < s.m; i++) c.verdict[s.lo + i] = st[i] == OURO_PACK_OK ? v[i] : 0;
+  if (c.kind == kRawBlock && c.body_hash) memcpy(c.body_hash + 32 * s.lo, s.h_out + O.be, 32 * s.m);
   if (hdr) {
     if (c.be) memcpy(c.be + 64 * s.lo, s.h_out + O.be, 64 * s.m);
     if (c.bl) memcpy(c.bl + 64 * s.lo, s.h_out + O.bl, 64 * s.m);
@@ -561,6 +572,7 @@ int raw_host_chain(const RawCall& c) {
 
 int raw_host(const RawCall& c) {
   if (c.kind == kRawByron) return raw_host_byron(c);
+  if (c.kind == kRawBlock) return block_host(c);
   if (c.kind == kRawChain) {
     try {  // (its lists are vectors; no exception crosses the C ABI)
       return raw_host_chain(c);

@@ -246,7 +246,8 @@ int stage_hdr(Stager& sg, const ouro_tpraos_batch* b, size_t lo, size_t m, Stage
 
 // ---- a raw-CBOR call (raw_pipe.cpp; multi.cpp shards one over devices) ----
 // (kRawChain: Byron and TPraos headers in one stream, classified per header)
-enum RawKind { kRawHdr = 0, kRawKes = 1, kRawByron = 2, kRawChain = 3 };
+// (kRawBlock: whole Shelley-family blocks, KES + body hash; block_api.cpp)
+enum RawKind { kRawHdr = 0, kRawKes = 1, kRawByron = 2, kRawChain = 3, kRawBlock = 4 };
 struct RawCall {
   RawKind kind;
   const uint8_t* raw;
@@ -265,8 +266,15 @@ struct RawCall {
   // an epoch-nonce schedule block (epoch_tab_build), or null; header / chain kinds
   const uint8_t* epochs = nullptr;
   size_t epochs_bytes = 0;
+  uint8_t* body_hash = nullptr;  // block kind: OUT, the computed bbHash (n x 32), or null
 };
 int raw_verify(const RawCall& c);
+// block_api.cpp: the block kind's device sequence on one stream (a: the
+// 64-byte aligned arena of cbor::block_layout(n)) and its host path
+int block_launch(hipStream_t st, const uint8_t* draw, size_t raw_bytes, const uint64_t* doff,
+                 const uint32_t* dlen, size_t n, uint64_t spkp, uint8_t* a, uint8_t* dstatus,
+                 uint8_t* dverdict, uint8_t* dbody_hash);
+int block_host(const RawCall& c);
 // the argument checks of a raw call that need no pass over the headers
 int raw_check(const RawCall& c);
 // the same call on the host path alone (ouro_chain_verify_cbor_host)
