@@ -238,7 +238,28 @@ int ouro_sum6kes_verify_batch(size_t n, const uint8_t *vk /* n x 32 */,
  * Footprint: the workspace belongs to the calling thread's pooled context, is
  * kept per stream for its next call and grows with the largest batch seen:
  * 4 x (the next power of two >= 2n) + 9n bytes, about 17 MB at 1M headers and
- * 1.1 MB per 65,536-header chunk of the pipelined paths. */
+ * 1.1 MB per 65,536-header chunk of the pipelined paths.
+ *
+ * Shared VRF key tables (deployment knob OURO_VRFKEY_SHARE, default 1): a
+ * pool's VRF key is the same 32 bytes in every header it forges.  The same
+ * GPU header batches group their headers by vrf_vk -- equality over all 32
+ * bytes -- run the key checks once per distinct key, build a fixed-base table
+ * of -Y for it, and compute both U = [s]B - [c]Y of every header from that
+ * table by additions alone.  U is a group element determined by (Y, c, s) and
+ * its encoding is canonical, so verdicts and outputs are bit for bit those of
+ * the per-header chains.  The grouping and the tables are rebuilt inside
+ * every call; nothing is cached between calls.  A batch with fewer than 16
+ * headers per distinct key, or with more distinct keys than the table budget
+ * holds, runs the per-header chains as before.  OURO_VRFKEY_SHARE=0 turns the
+ * sharing off.  The latency plans, the host path and the standalone VRF entry
+ * never share.
+ * Footprint: per stream of the calling thread's pooled context, kept for its
+ * next call: the grouping buffer, 4 x (the next power of two >= 2n) + 12n
+ * bytes (about 21 MB at 1M headers), and the tables, 90,752 bytes per key for
+ * min(n / 16, budget) keys -- at most OURO_VRFKEY_TAB_MB megabytes (default
+ * 512: 5,900 keys; a 65,536-header chunk of the pipelined paths sizes for
+ * 4,096 keys, 372 MB per slot in flight).  Lower the budget to trade memory
+ * for speed; a batch whose keys do not fit loses nothing but the saving. */
 typedef struct ouro_tpraos_batch {
   size_t n;
   const uint8_t *issuer_vk;        /* n x 32  bheaderVk (cold key)            */

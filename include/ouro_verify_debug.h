@@ -22,7 +22,7 @@ int ouro_debug_host_path(unsigned long long *single_items,
                          unsigned long long *recomputed_batches);
 
 /* Re-read the library's environment switches (OURO_SINGLE_ITEM,
- * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_BLOCK_SORT, OURO_HOST_*, OURO_CBOR_*,
+ * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_VRFKEY_*, OURO_BLOCK_SORT, OURO_HOST_*, OURO_CBOR_*,
  * OURO_LAT_*, OURO_PLAN_*; csrc/knobs.h).  The library reads them once, on
  * first use, and never on a call path: a process that changes one (tests,
  * bench.py A/B passes) calls this afterwards.  Plans keep the values they
@@ -84,6 +84,16 @@ int ouro_debug_test_hooks(void);
  * (OURO_OCERT_SHARE=0).  Synchronises the stream: for tests only.  Negative:
  * an OURO_E* status. */
 int ouro_debug_last_ocert_groups(void *stream);
+
+/* The distinct VRF keys (vrf_vk, see OURO_VRFKEY_SHARE in ouro_verify.h) that
+ * the calling thread's last header launch on `stream` found in its batch, and
+ * in *shared (may be NULL) whether that launch computed U from per-key tables
+ * (1) or ran the per-header chains (0: more keys than the tables were sized
+ * for).  Returns 0 with *shared = 0 when the launch did no grouping
+ * (OURO_VRFKEY_SHARE=0, or a batch too small or a budget too low for one
+ * key).  Synchronises the stream: for tests only.  Negative: an OURO_E*
+ * status. */
+int ouro_debug_last_vrfkey_groups(void *stream, int *shared);
 
 /* The calling thread's last raw-CBOR call (ouro_tpraos_verify_cbor /
  * ouro_integrity_verify_cbor): out6 = {total ms, ms gathering header bytes

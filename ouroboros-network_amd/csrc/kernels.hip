@@ -34,6 +34,7 @@
 #include "leader.h"
 #include "task_pool.h"
 #include "tpraos.h"
+#include "vrfkey_ws.h"
 #include "launches.h"
 #include "runtime.h"
 
@@ -199,11 +200,11 @@ constexpr int kOcertProbeCap = 64;
 // table; the keys compared were written before the launch, so no fence is
 // needed.  hash_mask: all ones (the test build's OURO_TEST_OCERT_HASH_BITS
 // narrows it to exercise probe chains and the cap).
-__global__ void __launch_bounds__(kBlock) k_ocert_group(ouro_tpraos_batch b, uint32_t* table,
-                                                        uint32_t cap_mask, uint32_t hash_mask,
-                                                        uint32_t* __restrict__ rep,
-                                                        uint32_t* __restrict__ uniq,
-                                                        uint32_t* ctr) {
+template <class Key>
+__device__ __forceinline__ void group_pass(const ouro_tpraos_batch& b, uint32_t* table,
+                                           uint32_t cap_mask, uint32_t hash_mask,
+                                           uint32_t* __restrict__ rep,
+                                           uint32_t* __restrict__ uniq, uint32_t* ctr) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nth = (size_t)gridDim.x * blockDim.x;
   const uint32_t lid = threadIdx.x & 63u;
@@ -211,18 +212,18 @@ __global__ void __launch_bounds__(kBlock) k_ocert_group(ouro_tpraos_batch b, uin
     const size_t i = base + lid;
     bool is_rep = false;
     if (i < b.n) {
-      uint32_t key[kOcertKeyWords];
-      ocert_key_load(key, b, i);
-      const uint64_t h = ocert_key_hash_words(key);
+      uint32_t key[Key::kWords];
+      Key::load(key, b, i);
+      const uint64_t h = Key::hash(key);
       uint32_t slot = (uint32_t)(h ^ (h >> 32)) & hash_mask & cap_mask;
       uint32_t r = (uint32_t)i;
       is_rep = true;  // also when the probe cap is reached
       for (int probe = 0; probe < kOcertProbeCap; probe++) {
         const uint32_t prev = atomicCAS(&table[slot], 0u, (uint32_t)i + 1u);
         if (prev == 0u) break;
-        uint32_t other[kOcertKeyWords];
-        ocert_key_load(other, b, prev - 1u);
-        if (ocert_key_equal_words(key, other)) {
+        uint32_t other[Key::kWords];
+        Key::load(other, b, prev - 1u);
+        if (Key::equal(key, other)) {
           r = prev - 1u;
           is_rep = false;
           break;
@@ -239,6 +240,86 @@ __global__ void __launch_bounds__(kBlock) k_ocert_group(ouro_tpraos_batch b, uin
       at = __shfl(at, __ffsll((long long)m) - 1);
       if (is_rep) uniq[at + __popcll(m & ((1ull << lid) - 1ull))] = (uint32_t)i;
     }
+  }
+}
+// (the key loaders: tpraos.h OcertKey, the 144 certificate bytes, and VrfKey,
+// the 32 bytes of vrf_vk)
+__global__ void __launch_bounds__(kBlock) k_ocert_group(ouro_tpraos_batch b, uint32_t* table,
+                                                        uint32_t cap_mask, uint32_t hash_mask,
+                                                        uint32_t* __restrict__ rep,
+                                                        uint32_t* __restrict__ uniq,
+                                                        uint32_t* ctr) {
+  group_pass<OcertKey>(b, table, cap_mask, hash_mask, rep, uniq, ctr);
+}
+__global__ void __launch_bounds__(kBlock) k_vrfkey_group(ouro_tpraos_batch b, uint32_t* table,
+                                                         uint32_t cap_mask, uint32_t hash_mask,
+                                                         uint32_t* __restrict__ rep,
+                                                         uint32_t* __restrict__ uniq,
+                                                         uint32_t* ctr) {
+  group_pass<VrfKey>(b, table, cap_mask, hash_mask, rep, uniq, ctr);
+}
+
+// ---- one fixed-base table of -Y per distinct VRF key (OURO_VRFKEY_SHARE) -----
+// A pool's VRF key is the same 32 bytes in every header it forges.  Per call
+// (nothing is kept between calls), after k_vrfkey_group has found the K
+// distinct keys (krep[i], kuniq[0 .. K)):
+//   k_vrfkey_base  key k on one lane: its flag (the checks of vrf_u_core), its
+//                  window base points (verify.h vrfkey_base) and
+//                  kidx[kuniq[k]] = k, so header i finds its table at
+//                  kidx[krep[i]];
+//   k_vrfkey_fill  (key, window) on one lane: the window's entries;
+//   k_tpraos_verify runs both U cores from the tables: additions only.
+// K stays on the device.  Above kmax keys (too few headers per key, or the
+// tables would not fit the budget: vrfkey_ws.h) the two build kernels return
+// at once and the header kernel runs the inline U cores, a wave-uniform
+// choice like the certificates'.
+// (the header kernel takes one pointer to this record in device memory, null
+// when sharing is off; k_vrfkey_base writes it from its own arguments, so the
+// header kernel holds two registers for it, not twelve)
+struct VrfKeyShare {
+  const uint32_t* count = nullptr;  // K
+  const uint32_t* krep = nullptr;
+  const uint32_t* kidx = nullptr;
+  const uint8_t* kflag = nullptr;
+  const int32_t* ktab = nullptr;    // key k at ktab + k * kYKeyWords
+  const int32_t* ubtab = nullptr;   // the chain's fixed-base table (verify.h build_ubtab)
+  uint32_t kmax = 0;
+};
+static_assert(sizeof(VrfKeyShare) <= 64, "the record's place in the grouping buffer (vrfkey_ws.h)");
+__global__ void __launch_bounds__(64) k_vrfkey_base(ouro_tpraos_batch b,
+                                                    const uint32_t* __restrict__ ctr,
+                                                    const uint32_t* __restrict__ uniq,
+                                                    uint32_t* __restrict__ kidx,
+                                                    uint8_t* __restrict__ kflag, int32_t* kbase,
+                                                    uint32_t kmax, VrfKeyShare desc,
+                                                    VrfKeyShare* out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *out = desc;
+  const uint32_t count = *ctr;
+  if (count > kmax) return;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += nth) {
+    const size_t i = uniq[k];
+    uint32_t p[8];
+    ld_words(p, b.vrf_vk + 32 * i, 2);
+    kflag[k] = vrfkey_base(p, kbase + k * kYBaseWords) ? 1 : 0;
+    kidx[i] = (uint32_t)k;
+  }
+}
+__global__ void __launch_bounds__(64) k_vrfkey_fill(const uint32_t* __restrict__ ctr,
+                                                    const int32_t* __restrict__ kbase,
+                                                    int32_t* ktab, uint32_t kmax) {
+  const uint32_t count = *ctr;
+  if (count > kmax) return;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  // consecutive lanes take one window of consecutive keys, so a wave's lanes
+  // all have the same entry count
+  const size_t keys64 = ((size_t)count + 63) / 64 * 64;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < keys64 * kYWindows; t += nth) {
+    const size_t blk = t / (64 * (size_t)kYWindows), r = t % (64 * (size_t)kYWindows);
+    const size_t k = blk * 64 + (r & 63);
+    const int j = (int)(r >> 6);
+    if (k >= count) continue;
+    vrfkey_fill(kbase + k * kYBaseWords, ktab + k * kYKeyWords, j);
   }
 }
 
@@ -266,11 +347,24 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_ocert_unique(
   }
 }
 
+// A U core of header i from its key's table, out of line with its own register
+// allocation (like the finish): the header kernel's own spills stay where
+// they were without it.
+__device__ __noinline__ void hdr_u_shared_ni(const ouro_tpraos_batch& b, size_t i, bool leader,
+                                             Slot lane, Slot res, const VrfKeyShare* ks) {
+  const uint32_t k = ks->kidx[ks->krep[i]];
+  hdr_u_shared(b, i, leader, ks->kflag[k] != 0, lane, res, ks->ubtab,
+               ks->ktab + (size_t)k * kYKeyWords);
+}
+
 // Throughput mode: one lane per header runs every core of tpraos.h, sharing
 // the VRF key decode and its table, then the single-inversion finish.
 // rep / ocert_ok / ocert_count (all null when sharing is off): the OCERT
 // verdicts of the unique pass; with at most kOcertShareMax(n) distinct
 // certificates the OCERT core is not run here (a wave-uniform choice).
+// ks (null when sharing is off): the per-key VRF tables; with at most
+// ks->kmax distinct keys both U cores run from them (hdr_u_shared_ni), and no
+// key is decoded or tabulated here.
 __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tpraos_batch b,
                                                              uint8_t* __restrict__ verdict,
                                                              uint8_t* __restrict__ beta_eta,
@@ -280,7 +374,8 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tprao
                                                              const uint32_t* __restrict__ rep,
                                                              const uint8_t* __restrict__ ocert_ok,
                                                              const uint32_t* __restrict__ ocert_count,
-                                                             uint32_t xopts) {
+                                                             uint32_t xopts,
+                                                             const VrfKeyShare* ks) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nth = (size_t)gridDim.x * blockDim.x;
   const Slot lane = slot_of(scratch, tid, kHdrLaneWords);
@@ -288,6 +383,8 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tprao
   const uint32_t opts = batch_opts(b) | xopts;  // xopts: kOptEpochs (launch_hdr)
   const bool shared = ocert_count != nullptr && *ocert_count <= kOcertShareMax(b.n);
   const int core0 = shared ? kCoreKes : kCoreOcert;
+  // both U cores from the key's table (ks: null when sharing is off)
+  const bool kshared = ks != nullptr && *ks->count <= ks->kmax;
 #if OURO_CLOCK_STAMPS
   unsigned long long c0 = 0, r0 = 0;
   if (threadIdx.x == 0) {
@@ -300,12 +397,23 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_tpraos_verify(ouro_tprao
 #if OURO_HDR_LOOP
     // one copy of the core dispatch, the core chosen at run time
 #pragma unroll 1
-    for (int c = core0; c <= kCoreVl; c++) hdr_core(b, i, opts, c, lane, res, btab);
+    for (int c = core0; c <= kCoreVl; c++) {
+      if (kshared && (c == kCoreUe || c == kCoreUl)) {
+        hdr_u_shared_ni(b, i, c == kCoreUl, lane, res, ks);
+        continue;
+      }
+      hdr_core(b, i, opts, c, lane, res, btab);
+    }
 #else
     if (!shared) hdr_core(b, i, opts, kCoreOcert, lane, res, btab);
     hdr_core(b, i, opts, kCoreKes, lane, res, btab);
-    hdr_core(b, i, opts, kCoreUe, lane, res, btab);
-    hdr_core(b, i, opts, kCoreUl, lane, res, btab);
+    if (kshared) {
+      hdr_u_shared_ni(b, i, false, lane, res, ks);
+      hdr_u_shared_ni(b, i, true, lane, res, ks);
+    } else {
+      hdr_core(b, i, opts, kCoreUe, lane, res, btab);
+      hdr_core(b, i, opts, kCoreUl, lane, res, btab);
+    }
     hdr_core(b, i, opts, kCoreVe, lane, res, btab);
     hdr_core(b, i, opts, kCoreVl, lane, res, btab);
 #endif
@@ -935,6 +1043,7 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b_in, uint8_t* verdict, 
       if ((rc = launch_check())) return rc;
     }
     ctx().ocert[st].last = nullptr;
+    ctx().vrfkey[st].last = nullptr;
     return OURO_OK;
   }
   // One OCERT verification per distinct certificate (see k_ocert_group); the
@@ -978,8 +1087,52 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b_in, uint8_t* verdict, 
   } else if ((rc = plan(ds, kHdr, b.n, st, &grid, &scr, kHdrLaneWords))) {
     return rc;
   }
+  // One fixed-base table of -Y per distinct VRF key (see k_vrfkey_base).  The
+  // tables are sized on the host for kmax keys (vrfkey_ws.h); the count stays
+  // on the device and the kernels compare it with kmax.
+  VrfKeyWs& kw = ctx().vrfkey[st];
+  kw.last = nullptr;
+  const VrfKeyShare* ks = nullptr;
+  const VrfKeyLayout L =
+      vrfkey_share() ? vrfkey_layout(b.n, kYKeyBytes, vrfkey_tab_bytes()) : VrfKeyLayout{};
+  if (L.kmax) {
+    if ((rc = ensure(kw.group, L.group_bytes))) return rc;
+    if ((rc = ensure(kw.tables, L.table_bytes))) return rc;
+    uint8_t* g = static_cast<uint8_t*>(kw.group.p);
+    uint32_t* ctr = reinterpret_cast<uint32_t*>(g);
+    VrfKeyShare* desc = reinterpret_cast<VrfKeyShare*>(g + L.off_desc);
+    uint32_t* table = reinterpret_cast<uint32_t*>(g + L.off_table);
+    uint32_t* krep = reinterpret_cast<uint32_t*>(g + L.off_rep);
+    uint32_t* kuniq = reinterpret_cast<uint32_t*>(g + L.off_uniq);
+    uint32_t* kidx = reinterpret_cast<uint32_t*>(g + L.off_kidx);
+    uint8_t* kflag = g + L.off_flag;
+    // a key's table first (128-B entries on 128-B lines), the base points after
+    int32_t* ktab = static_cast<int32_t*>(kw.tables.p);
+    int32_t* kbase = ktab + L.kmax * kYKeyWords;
+    const uint32_t kmax = (uint32_t)L.kmax;
+    OURO_HIP(hipMemsetAsync(ctr, 0, L.off_rep, st));
+    const size_t gg = (b.n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_vrfkey_group, dim3((unsigned)gg), dim3(kBlock), 0, st, b, table,
+                       (uint32_t)(L.cap - 1), ocert_hash_mask(), krep, kuniq, ctr);
+    // one wave per workgroup: the few lanes of a build spread over the CUs
+    VrfKeyShare d;
+    d.count = ctr;
+    d.krep = krep;
+    d.kidx = kidx;
+    d.kflag = kflag;
+    d.ktab = ktab;
+    d.ubtab = ds->ubtab;
+    d.kmax = kmax;
+    hipLaunchKernelGGL(k_vrfkey_base, dim3((unsigned)((L.kmax + 63) / 64)), dim3(64), 0, st, b,
+                       ctr, kuniq, kidx, kflag, kbase, kmax, d, desc);
+    hipLaunchKernelGGL(k_vrfkey_fill, dim3((unsigned)((L.kmax + 63) / 64 * kYWindows)), dim3(64),
+                       0, st, ctr, kbase, ktab, kmax);
+    ks = desc;
+    kw.last = ctr;
+    kw.last_kmax = kmax;
+  }
   hipLaunchKernelGGL(k_tpraos_verify, dim3(grid), dim3(kBlock), 0, st, b, verdict, be, bl, scr,
-                     ds->btab, rep, ocert_ok, count, xopts);
+                     ds->btab, rep, ocert_ok, count, xopts, ks);
   return launch_check();
 }
 

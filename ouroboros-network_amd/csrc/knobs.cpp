@@ -38,6 +38,8 @@ void load(Knobs& k) {
   read_int(k.host_threads, "OURO_HOST_THREADS", 0);
   k.host_lanes.store(str_is("OURO_HOST_IMPL", "lanes"), std::memory_order_relaxed);
   read_int(k.ocert_share, "OURO_OCERT_SHARE", 1);
+  read_int(k.vrfkey_share, "OURO_VRFKEY_SHARE", 1);
+  read_int<long long>(k.vrfkey_tab_mb, "OURO_VRFKEY_TAB_MB", 512);
   read_size<size_t>(k.cbor_chunk, "OURO_CBOR_CHUNK", 0);
   read_size<size_t>(k.cbor_slots, "OURO_CBOR_SLOTS", 0);
   read_size<size_t>(k.cbor_copy_threads, "OURO_CBOR_COPY_THREADS", 0);

@@ -27,6 +27,8 @@ struct Knobs {
   std::atomic<int> host_threads{0};          // OURO_HOST_THREADS (0: the default cap)
   std::atomic<int> host_lanes{0};            // OURO_HOST_IMPL=lanes (A/B, bench single_item)
   std::atomic<int> ocert_share{1};           // OURO_OCERT_SHARE (0: every header's own OCERT check)
+  std::atomic<int> vrfkey_share{1};          // OURO_VRFKEY_SHARE (0: every header's own U chains)
+  std::atomic<long long> vrfkey_tab_mb{512}; // OURO_VRFKEY_TAB_MB (per-stream budget of the key tables)
   // raw CBOR engine (0: the default; range-checked where used)
   std::atomic<size_t> cbor_chunk{0};         // OURO_CBOR_CHUNK
   std::atomic<size_t> cbor_slots{0};         // OURO_CBOR_SLOTS

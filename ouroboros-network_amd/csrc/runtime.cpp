@@ -79,12 +79,20 @@ int device_state(DeviceState** out) {
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
       return fail(OURO_ENODEV, std::string("device is ") + prop.gcnArchName + ", need gfx950");
     s.cus = prop.multiProcessorCount;
-    // niels B tables, then their wave-wide form (latency mode, wide.h)
-    std::vector<int32_t> tab(kBTabWords + kBTabWideWords);
+    // niels B tables, then their wave-wide form (latency mode, wide.h), then
+    // the doubling-free U chain's table (built once per process)
+    static const std::vector<int32_t>* const utab = [] {
+      auto* t = new std::vector<int32_t>(kUBTabWords);
+      build_ubtab(t->data());
+      return t;
+    }();
+    std::vector<int32_t> tab(kBTabWords + kBTabWideWords + kUBTabWords);
+    memcpy(tab.data() + kBTabWords + kBTabWideWords, utab->data(), sizeof(int32_t) * kUBTabWords);
     memcpy(tab.data(), ouro_host::btab(), sizeof(int32_t) * kBTabWords);  // built once per process
     build_btab_wide(reinterpret_cast<uint16_t*>(tab.data() + kBTabWords), tab.data());
     OURO_HIP(hipMalloc(&s.btab, sizeof(int32_t) * tab.size()));
     OURO_HIP(hipMemcpy(s.btab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
+    s.ubtab = s.btab + kBTabWords + kBTabWideWords;
     for (int id = 0; id < kNumKernels; id++) {
       int per_cu = 0;
       OURO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_ptr(id), kBlock, 0));
@@ -219,6 +227,18 @@ bool split_launch() {
 // (kernels.hip k_ocert_group; OURO_OCERT_SHARE=0: every header's own check,
 // with no group or unique pass).
 bool ocert_share() { return ouro_knobs::get().ocert_share.load(std::memory_order_relaxed) != 0; }
+
+// Header batches build one fixed-base table of -Y per distinct VRF key and
+// run both U cores from it (kernels.hip k_vrfkey_base; OURO_VRFKEY_SHARE=0:
+// every header's own doubling chain, with no group or build pass).  The
+// tables of one stream take at most OURO_VRFKEY_TAB_MB (default 512, which
+// holds 5,900 keys at width 6); a batch with more distinct keys than fit, or
+// with fewer than vrfkey_ws.h kVrfKeyMinPerKey headers per key, runs inline.
+bool vrfkey_share() { return ouro_knobs::get().vrfkey_share.load(std::memory_order_relaxed) != 0; }
+size_t vrfkey_tab_bytes() {
+  const long long mb = ouro_knobs::get().vrfkey_tab_mb.load(std::memory_order_relaxed);
+  return mb <= 0 ? 0 : (size_t)std::min<long long>(mb, 1ll << 20) << 20;
+}
 
 // The bits of the certificate hash the group pass uses.  The test-hook build
 // narrows them (OURO_TEST_OCERT_HASH_BITS=k) so that a few hundred headers
@@ -384,6 +404,26 @@ int ouro_debug_last_ocert_groups(void* stream) {
   OURO_HIP(hipStreamSynchronize(st));
   uint32_t count = 0;
   OURO_HIP(hipMemcpy(&count, it->second.last, sizeof count, hipMemcpyDeviceToHost));
+  return (int)count;
+}
+
+// DIAGNOSTIC (tests): the distinct VRF keys the last header launch of the
+// calling thread on `stream` found (runtime.h VrfKeyWs), and in *shared
+// whether that launch ran the U cores from per-key tables; 0 and not shared
+// when it did no grouping.  Synchronises the stream.
+int ouro_debug_last_vrfkey_groups(void* stream, int* shared) {
+  if (shared) *shared = 0;
+  int dev;
+  int rc = current_device(&dev);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ThreadCtx& c = ctx_of(dev);
+  auto it = c.vrfkey.find(st);
+  if (it == c.vrfkey.end() || !it->second.last) return 0;
+  OURO_HIP(hipStreamSynchronize(st));
+  uint32_t count = 0;
+  OURO_HIP(hipMemcpy(&count, it->second.last, sizeof count, hipMemcpyDeviceToHost));
+  if (shared) *shared = count <= it->second.last_kmax ? 1 : 0;
   return (int)count;
 }
 

@@ -42,6 +42,7 @@ struct DeviceState {
   int err = OURO_OK;
   std::string err_msg;
   int32_t* btab = nullptr;
+  int32_t* ubtab = nullptr;  // inside btab's allocation: the U chain's table (verify.h build_ubtab)
   int cus = 0;
   int max_blocks[16] = {0};  // per KernelId (kNumKernels <= 16)
 };
@@ -148,10 +149,23 @@ struct OcertWs {
   const uint32_t* last = nullptr;
 };
 
+// The VRF key sharing workspace of one stream (kernels.hip launch_hdr,
+// vrfkey_ws.h): the grouping buffer (80 + 4 (next power of two >= 2n) + 12n
+// bytes and a flag per key) and the tables of up to kmax keys (verify.h kYKeyBytes
+// each, at most OURO_VRFKEY_TAB_MB in all).  last / last_kmax: the device
+// count of the stream's last header launch and the kmax it ran with (null
+// when that launch built no tables), for ouro_debug_last_vrfkey_groups.
+struct VrfKeyWs {
+  Buf group, tables;
+  const uint32_t* last = nullptr;
+  uint32_t last_kmax = 0;
+};
+
 struct ThreadCtx {
   hipStream_t stream = nullptr;
   std::map<hipStream_t, Buf> scratch;  // per stream: concurrent launches never share slots
   std::map<hipStream_t, OcertWs> ocert;  // per stream, grown like scratch
+  std::map<hipStream_t, VrfKeyWs> vrfkey;  // per stream, grown like scratch
   Buf in[32];  // staging slots; a header batch uses up to 24
   Pipe pipe;
   RawPipe raw;  // ouro_tpraos_verify_cbor / ouro_integrity_verify_cbor
@@ -194,6 +208,8 @@ size_t wide_small_max();
 bool split_launch();
 bool ocert_share();
 uint32_t ocert_hash_mask();
+bool vrfkey_share();
+size_t vrfkey_tab_bytes();
 int lat_block();
 int lat_quad();
 int lat_wide_mask();

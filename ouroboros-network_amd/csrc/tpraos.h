@@ -489,6 +489,66 @@ OURO_HD inline bool ocert_key_equal(const ouro_tpraos_batch& b, size_t i, size_t
   return ocert_key_equal_words(a, c);
 }
 
+// ---- the VRF key as a key (kernels.hip k_vrfkey_group) ---------------------
+// Headers whose 32 vrf_vk bytes are equal share one fixed-base table of -Y
+// per batch (verify.h vrfkey_*).  As with certificates, equality over ALL of
+// the bytes is the correctness condition; the hash only picks a table slot.
+constexpr int kVrfKeyWords = 8;
+OURO_FI void vrfkey_load(uint32_t w[kVrfKeyWords], const ouro_tpraos_batch& b, size_t i) {
+  ld_words(w, b.vrf_vk + 32 * i, 2);
+}
+OURO_FI uint64_t vrfkey_hash_words(const uint32_t w[kVrfKeyWords]) {
+  uint64_t h = 0x9e3779b97f4a7c15ull;
+#pragma unroll
+  for (int k = 0; k < kVrfKeyWords; k += 2) {
+    h ^= (uint64_t)w[k] | ((uint64_t)w[k + 1] << 32);
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 29;
+  }
+  return h;
+}
+OURO_FI bool vrfkey_equal_words(const uint32_t a[kVrfKeyWords], const uint32_t c[kVrfKeyWords]) {
+  uint32_t diff = 0;
+#pragma unroll
+  for (int k = 0; k < kVrfKeyWords; k++) diff |= a[k] ^ c[k];
+  return diff == 0;
+}
+// the group pass's key loaders (kernels.hip group_pass)
+struct OcertKey {
+  static constexpr int kWords = kOcertKeyWords;
+  static OURO_FI void load(uint32_t* w, const ouro_tpraos_batch& b, size_t i) { ocert_key_load(w, b, i); }
+  static OURO_FI uint64_t hash(const uint32_t* w) { return ocert_key_hash_words(w); }
+  static OURO_FI bool equal(const uint32_t* a, const uint32_t* c) { return ocert_key_equal_words(a, c); }
+};
+struct VrfKey {
+  static constexpr int kWords = kVrfKeyWords;
+  static OURO_FI void load(uint32_t* w, const ouro_tpraos_batch& b, size_t i) { vrfkey_load(w, b, i); }
+  static OURO_FI uint64_t hash(const uint32_t* w) { return vrfkey_hash_words(w); }
+  static OURO_FI bool equal(const uint32_t* a, const uint32_t* c) { return vrfkey_equal_words(a, c); }
+};
+
+// A U core of header i from its key's table (verify.h vrf_u_fixed_lane): the
+// key's flag comes from the per-key pass, and nothing of the key is decoded
+// or tabulated here.
+OURO_HD inline void hdr_u_shared(const ouro_tpraos_batch& b, size_t i, bool leader, bool key_ok,
+                                 Slot lane, Slot res, const int32_t* ubtab,
+                                 const int32_t* ytab) {
+  uint32_t pi[20];
+  ld_words(pi, (leader ? b.leader_proof : b.eta_proof) + 80 * i, 5);
+  uint32_t c[8], s_raw[8], s[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    s_raw[k] = pi[12 + k];
+    c[k] = k < 4 ? pi[8 + k] : 0u;
+  }
+  sc_reduce256(s, s_raw);
+  st_words8(lane + kSlotA1, c);
+  st_words8(lane + kSlotB, s);
+  vrf_u_fixed_lane(lane, ubtab, ytab);
+  st_point_from_dsm(res, leader ? kPtUl : kPtUe, lane);
+  stg1(res.word(kResFlags + (leader ? kCoreUl : kCoreUe)), key_ok ? kFlagOk : 0);
+}
+
 // ---- the epoch-nonce schedule (include/ouro_verify.h ouro_epoch_nonces) -----
 // One block, 16-byte aligned, in host or device memory, built by the runtime
 // from the caller's validated schedule (epoch_tab_fill):

@@ -562,6 +562,238 @@ OURO_FI ge_p2 dsm_result(Slot lane) {
   return ge_p2{ld_fe(lane + kSlotOut), ld_fe(lane + kSlotOut + 12), ld_fe(lane + kSlotOut + 24)};
 }
 
+// ---- per-key fixed-base tables of -Y (kernels.hip OURO_VRFKEY_SHARE) --------
+// A pool's VRF key Y is the same 32 bytes in every header it forges, so the
+// header launch builds, once per distinct key of the batch, the table
+//   m 2^(w j) (-Y),  m = 1 .. 2^(w-1),  window j = 0 .. kYWindows - 1
+// (w = kYW) and every header's U = [s]B - [c]Y becomes additions only: the
+// 128-bit c in signed w-bit digits picks one entry per window.  The top window
+// holds c's bits above w (kYWindows - 1) plus the recoding carry, so its
+// digits are 0 .. kYTopEntries and it stores only that many entries.
+// Entries are 32 plain contiguous words (the packed cached form of the
+// per-lane tables: one 128-B line each); a key's windows are stored back to
+// back.  kYBaseWords: the window base points 2^(w j)(-Y) as p3 (four elements
+// at a 12-word stride), written by the per-key pass for the table fill.
+#ifndef OURO_YW
+#define OURO_YW 6
+#endif
+constexpr int kYW = OURO_YW;
+static_assert(kYW >= 4 && kYW <= 8, "OURO_YW: 4 .. 8");
+constexpr int kYWindows = (128 + kYW) / kYW;                  // 22 at w = 6, 17 at w = 8
+constexpr int kYWinEntries = 1 << (kYW - 1);
+constexpr int kYTopEntries = (1 << (128 - kYW * (kYWindows - 1))) - 1 + 1;  // top bits + carry
+static_assert(kYTopEntries <= kYWinEntries, "the top window's digits fit a window");
+constexpr int kYKeyEntries = (kYWindows - 1) * kYWinEntries + kYTopEntries;  // 676 / 2,049
+constexpr size_t kYKeyWords = (size_t)kYKeyEntries * kPackedWords;
+constexpr int kYBasePtWords = 48;
+constexpr size_t kYBaseWords = (size_t)kYWindows * kYBasePtWords;
+constexpr size_t kYKeyBytes = 4 * (kYKeyWords + kYBaseWords);  // 90,752 B at w = 6
+
+// one element / one packed entry in plain (not slot-interleaved) memory
+OURO_FI void st_fe_at(int32_t* p, const fe& f) {
+  stg4(p, make_int4(f.v[0], f.v[1], f.v[2], f.v[3]));
+  stg4(p + 4, make_int4(f.v[4], f.v[5], f.v[6], f.v[7]));
+  stg2(p + 8, make_int2(f.v[8], f.v[9]));
+  OURO_TRK(ouro_trk_store(p, f.b));
+}
+OURO_FI fe ld_fe_at(const int32_t* p) {
+  const int4 a = ldg4(p), b = ldg4(p + 4);
+  const int2 c = ldg2(p + 8);
+  fe f = fe_make(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y);
+  OURO_TRK(ouro_trk_load(p, f.b));
+  return f;
+}
+OURO_FI void st_cached_packed_at(int32_t* p, const ge_cached& c) {
+  const fe* s[4] = {&c.YplusX, &c.YminusX, &c.Z2, &c.T2d};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    uint32_t w[8];
+    fe_pack256(w, *s[k]);
+    stg4(p + 8 * k, make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]));
+    stg4(p + 8 * k + 4, make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]));
+  }
+}
+OURO_FI ge_cached ld_cached_packed_at(const int32_t* p) {
+  fe f[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int4 a = ldg4(p + 8 * k), b = ldg4(p + 8 * k + 4);
+    const uint32_t w[8] = {(uint32_t)a.x, (uint32_t)a.y, (uint32_t)a.z, (uint32_t)a.w,
+                           (uint32_t)b.x, (uint32_t)b.y, (uint32_t)b.z, (uint32_t)b.w};
+    f[k] = fe_unpack256(w);
+  }
+  return ge_cached{f[0], f[1], f[2], f[3]};
+}
+
+// The per-key pass: the key checks of vrf_u_core (tpraos.h) and the window
+// base points 2^(w j)(-Y), a serial chain of w (kYWindows - 1) doublings.  A
+// key that fails a check still gets its points (of whatever the decode left):
+// its headers are rejected by the flag, as they are with the inline core.
+OURO_HD inline bool vrfkey_base(const uint32_t pk[8], int32_t* base) {
+  ge_p3 Y;
+  bool ok = !ge_has_small_order(pk) && ge_is_canonical(pk);
+  ok = ge_decode(&Y, pk, false) && ok;
+  ge_p3 P = ge_p3_neg(Y);
+#pragma unroll 1
+  for (int j = 0; j < kYWindows; j++) {
+    int32_t* b = base + j * kYBasePtWords;
+    st_fe_at(b, P.X);
+    st_fe_at(b + 12, P.Y);
+    st_fe_at(b + 24, P.Z);
+    st_fe_at(b + 36, P.T);
+    if (j + 1 == kYWindows) break;
+    ge_p1p1 t = ge_p3_dbl(P);
+#pragma unroll 1
+    for (int k = 1; k < kYW; k++) t = dsm_dbl(t);
+    P = ge_p1p1_to_p3(t);
+  }
+  return ok;
+}
+// entries of window j, and where they start in a key's table
+OURO_FI int vrfkey_win_entries(int j) { return j + 1 < kYWindows ? kYWinEntries : kYTopEntries; }
+OURO_FI size_t vrfkey_win_word(int j) { return (size_t)j * kYWinEntries * kPackedWords; }
+// The table fill of one (key, window): m P_j for m = 1 .. its entry count
+OURO_HD inline void vrfkey_fill(const int32_t* base, int32_t* tab, int j) {
+  const int32_t* b = base + j * kYBasePtWords;
+  const ge_p3 P{ld_fe_at(b), ld_fe_at(b + 12), ld_fe_at(b + 24), ld_fe_at(b + 36)};
+  int32_t* e = tab + vrfkey_win_word(j);
+  const int n = vrfkey_win_entries(j);
+  const ge_cached c1 = ge_p3_to_cached(P);
+  st_cached_packed_at(e, c1);
+  if (n < 2) return;
+  ge_p3 Pk = ge_p1p1_to_p3(ge_p3_dbl(P));
+  st_cached_packed_at(e + kPackedWords, ge_p3_to_cached(Pk));
+#pragma unroll 1
+  for (int m = 2; m < n; m++) {
+    Pk = ge_p1p1_to_p3(ge_add_cached(Pk, c1, false));
+    st_cached_packed_at(e + m * kPackedWords, ge_p3_to_cached(Pk));
+  }
+}
+
+// 128-bit stream shifted right by 0 < bits < 32
+OURO_FI void ss_shr4(uint32_t w[4], int bits) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) w[i] = (w[i] >> bits) | (w[i + 1] << (32 - bits));
+  w[3] >>= bits;
+}
+
+// 256-bit stream shifted right by 0 < bits < 32
+OURO_FI void ss_shr8(uint32_t w[8], int bits) {
+#pragma unroll
+  for (int i = 0; i < 7; i++) w[i] = (w[i] >> bits) | (w[i + 1] << (32 - bits));
+  w[7] >>= bits;
+}
+
+// The fixed base of that chain.  dsm_body's B tables hold [m]B and
+// [m]2^128 B only -- its doublings supply the other powers of two -- so a chain
+// without doublings has a table of its own: m 2^(w k) B for every digit
+// position k of a scalar below 2^253, m = 1 .. 2^(w-1), w = kUBW, as affine
+// niels entries like the B tables (build_ubtab below; 22 x 2,048 entries,
+// 5.8 MB at the default w = 12, which keeps the number of B additions equal
+// to the number of Y additions at kYW = 6 and the table near an XCD's L2).
+#ifndef OURO_UBW
+#define OURO_UBW 12
+#endif
+constexpr int kUBW = OURO_UBW;
+static_assert(kUBW >= 8 && kUBW <= 16, "OURO_UBW: 8 .. 16");
+constexpr int kUBDigits = (253 + kUBW) / kUBW;       // the top digit never carries out
+constexpr int kUBWinEntries = 1 << (kUBW - 1);
+constexpr size_t kUBTabWords = (size_t)kUBDigits * kUBWinEntries * kNielsWords;
+
+// U = [b]B + [c](-Y) from the key's table `ytab` and the fixed-base table
+// `ubtab`: additions only, no doubling.  Reads c (128 bits) from kSlotA1 and
+// b (below 2^253) from kSlotB, like dsm_body, and writes the p2 result to
+// kSlotOut.  Trip j adds b's digit j and c's digit j, both recoded on the way
+// up: every scalar is consumed from its low end, so the streams shift right
+// and no recoding carries need storing.  The first addition starts from the
+// identity (dsm_body's `fresh`); a zero digit adds the identity.  Each lane
+// gathers its own 128-B entry from a table larger than L2, so trip j touches
+// trip j + 1's entries once its own Y entry is loaded: one addition (~5 k
+// cycles) of cover, and the touches queue behind the loads this trip waits
+// for, not in front of them.  Out of line with its own register allocation,
+// like dsm_lane.
+OURO_NI void vrf_u_fixed_lane(Slot lane, const int32_t* ubtab, const int32_t* ytab) {
+  uint32_t a[8], b[8];
+  ld_words8(a, lane + kSlotA1);
+  ld_words8(b, lane + kSlotB);
+  uint32_t c[4] = {a[0], a[1], a[2], a[3]};
+  constexpr uint32_t kYMask = (1u << kYW) - 1u, kBMask = (1u << kUBW) - 1u;
+  constexpr int kTrips = kYWindows > kUBDigits ? kYWindows : kUBDigits;
+  uint32_t cy = 0, cbw = 0;  // the recoding carries into the next digits
+  auto next_y = [&]() {
+    const uint32_t v = (c[0] & kYMask) + cy;
+    ss_shr4(c, kYW);
+    cy = v > (1u << (kYW - 1)) ? 1u : 0u;
+    return (int32_t)v - (int32_t)(cy << kYW);
+  };
+  auto next_b = [&]() {
+    const uint32_t v = (b[0] & kBMask) + cbw;
+    ss_shr8(b, kUBW);
+    cbw = v > (1u << (kUBW - 1)) ? 1u : 0u;
+    return (int32_t)v - (int32_t)(cbw << kUBW);
+  };
+  auto y_entry = [&](int j, int32_t d) {
+    const int mag = d < 0 ? -d : d;
+    return ytab + vrfkey_win_word(j) + (size_t)(mag > 0 ? mag - 1 : 0) * kPackedWords;
+  };
+  auto b_entry = [&](int j, int32_t d) {
+    const int mag = d < 0 ? -d : d;
+    return ubtab + ((size_t)j * kUBWinEntries + (mag > 0 ? mag - 1 : 0)) * kNielsWords;
+  };
+  int32_t dy = next_y(), db = next_b();
+  uint32_t prefetch = 0;
+  ge_p1p1 t{fe_zero(), fe_one(), fe_one(), fe_one()};
+  bool fresh = true;  // t is the identity (wave-uniform)
+#pragma unroll 1
+  for (int j = 0; j < kTrips; j++) {
+    const bool actB = j < kUBDigits, actY = j < kYWindows;
+    int32_t ny = 0, nb = 0;
+#pragma unroll 1
+    for (int src = 0; src < 2; src++) {
+      if (!(src == 0 ? actB : actY)) continue;
+      const int32_t d = src == 0 ? db : dy;
+      const bool neg = d < 0;
+      ge_cached q;
+      if (src == 0) {
+        const ge_niels nq = ld_niels(b_entry(j, d));
+        q = ge_cached{nq.yplusx, nq.yminusx, fe_two(), nq.xy2d};
+      } else {
+        q = ld_cached_packed_at(y_entry(j, d));
+      }
+      if (src == 1 || !actY) {
+        // the next trip's digits, and its entries touched behind this load
+        if (j + 1 < kYWindows) {
+          ny = next_y();
+          prefetch ^= (uint32_t)ldg1(y_entry(j + 1, ny));
+        }
+        if (j + 1 < kUBDigits) {
+          nb = next_b();
+          prefetch ^= (uint32_t)ldg1(b_entry(j + 1, nb));
+        }
+      }
+      if (d == 0) q = ge_cached_identity();
+      if (fresh) {
+        // t is still the identity: O +- q = (2x, 2y, 2z, 2z) with no multiply
+        const fe qa = fe_select(q.YminusX, q.YplusX, neg);
+        const fe qb = fe_select(q.YplusX, q.YminusX, neg);
+        t = ge_p1p1{fe_carry(fe_sub4(qa, qb)), fe_carry(fe_add(qa, qb)), q.Z2, q.Z2};
+        fresh = false;
+        continue;
+      }
+      t = ge_add_lockstep<false>(t, q, neg, src == 0);
+    }
+    dy = ny;
+    db = nb;
+  }
+  const ge_p2 r = ge_p1p1_to_p2(t);
+  st_fe(lane + kSlotOut, r.X);
+  st_fe(lane + kSlotOut + 12, r.Y);
+  st_fe(lane + kSlotOut + 24, r.Z);
+  // keeps the touches alive (dsm_body: the store, if it ever happens, lands on
+  // Z's padding word)
+  if (prefetch == 0xffffffffu) stg1(lane.word(kSlotOut + 35), (int32_t)prefetch);
+}
+
 // Phases of a core around its double-scalar multiplication (the split header
 // kernel, kernels.hip OURO_SPLIT): kPhasePre stops once the dsm's inputs
 // -- tables, scalars, recoding carries -- and its cfg word (kSlotCfg, the
@@ -992,13 +1224,13 @@ OURO_HD inline bool sum6kes_verify_lane(const uint32_t vk[8], uint32_t t, const 
 // limbs, for G = B and G = 2^128 B (the two halves of the split scalar).  The
 // affine conversion inverts the Z coordinates in chunks with one inversion each
 // (Montgomery's trick); 2 x 32768 entries take a few tens of ms on the host.
-inline void build_btab_one(int32_t* out, const ge_p3& G) {
+inline void build_btab_one(int32_t* out, const ge_p3& G, int entries = kBTabEntries) {
   constexpr int kChunk = 256;
   std::vector<ge_p3> pts(kChunk);
   std::vector<fe> pre(kChunk);
   ge_p3 P = G;
-  for (int k0 = 0; k0 < kBTabEntries; k0 += kChunk) {
-    const int n = kBTabEntries - k0 < kChunk ? kBTabEntries - k0 : kChunk;
+  for (int k0 = 0; k0 < entries; k0 += kChunk) {
+    const int n = entries - k0 < kChunk ? entries - k0 : kChunk;
     for (int i = 0; i < n; i++) {
       if (k0 + i > 0) P = ge_p3_add(P, G);
       pts[i] = P;
@@ -1035,6 +1267,20 @@ inline void build_btab(int32_t* out) {
   ge_p3 B128 = B;
   for (int i = 0; i < 128; i++) B128 = ge_p1p1_to_p3(ge_p3_dbl(B128));
   build_btab_one(out + (size_t)kBTabEntries * kNielsWords, B128);
+}
+
+// The doubling-free U chain's table (vrf_u_fixed_lane): [m] 2^(kUBW k) B for
+// k = 0 .. kUBDigits - 1, m = 1 .. kUBWinEntries, in the same niels form.
+inline void build_ubtab(int32_t* out) {
+  uint32_t by[8];
+  for (int i = 0; i < 8; i++) by[i] = 0x66666666u;
+  by[0] = 0x66666658u;
+  ge_p3 G;
+  ge_decode(&G, by, false);
+  for (int k = 0; k < kUBDigits; k++) {
+    build_btab_one(out + (size_t)k * kUBWinEntries * kNielsWords, G, kUBWinEntries);
+    for (int i = 0; i < kUBW; i++) G = ge_p1p1_to_p3(ge_p3_dbl(G));
+  }
 }
 
 // The fixed-base tables in the latency mode's wave-wide form (wide.h

@@ -49,8 +49,10 @@ def counts(header_only: bool = False):
     hdr = measure(lambda: d.dh_tpraos_verify(ctypes.addressof(st), 0, v.ctypes.data,
                                              be.ctypes.data, bl.ctypes.data))
     assert int(v[0]) & 0x0F == 15
+    shared = shared_counts(d, measure, st, hd.vrf_vk, (v, be, bl))
     if header_only:
-        return {"tpraos_header (throughput schedule)": hdr}
+        return {"tpraos_header (throughput schedule)": hdr,
+                "tpraos_header (shared VRF key tables)": shared}
     import oracle_ffi as O
 
     pk, sig, msg = O.synth_ed25519(1, first=0)
@@ -67,7 +69,32 @@ def counts(header_only: bool = False):
     kes = measure(lambda: d.dh_sum6kes_verify(hd.hot_vk, 0, hd.body, len(hd.body), hd.kes_sig))
     return {"ed25519_verify": ed, "vrf03_verify": vrf, "sum6kes_verify": kes,
             "tpraos_header (throughput schedule)": hdr,
+            "tpraos_header (shared VRF key tables)": shared,
             "canonical_M (SURVEY.md §8(d))": {"ed25519": 2983, "vrf": 7325, "header": 20616}}
+
+
+def shared_counts(d, measure, st, vrf_vk, want):
+    """The same header with both U cores from its key's fixed-base table
+    (OURO_VRFKEY_SHARE): the operations of one header, and separately those of
+    building one key's table (once per distinct key of a batch)."""
+    import numpy as np
+
+    w, nw, ne = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    tw, bw, r = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    d.dh_vrfkey_params(*(ctypes.byref(x) for x in (w, nw, ne, tw, bw, r)))
+    tab, base = np.zeros(tw.value, np.int32), np.zeros(bw.value, np.int32)
+    d.dh_vrfkey_build.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
+    key = measure(lambda: d.dh_vrfkey_build(bytes(vrf_vk), tab.ctypes.data, base.ctypes.data))
+    v, be, bl = np.zeros(1, np.uint8), np.zeros((1, 64), np.uint8), np.zeros((1, 64), np.uint8)
+    d.dh_tpraos_verify_shared.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] +
+                                          [ctypes.c_void_p] * 3)
+    run = lambda: d.dh_tpraos_verify_shared(ctypes.addressof(st), tab.ctypes.data, 1,  # noqa: E731
+                                            v.ctypes.data, be.ctypes.data, bl.ctypes.data)
+    run()  # the fixed-base table outside the counted region
+    out = measure(run)
+    assert (v == want[0]).all() and (be == want[1]).all() and (bl == want[2]).all()
+    out["per_key"] = dict(key, width=w.value, entries=ne.value, min_headers_per_key=r.value)
+    return out
 
 
 if __name__ == "__main__":
