@@ -647,6 +647,144 @@ int ouro_chain_verify_cbor_multi(const int *devices, int ndev, const uint8_t *ra
                                  uint8_t *verdict, uint8_t *beta_eta, uint8_t *beta_leader,
                                  uint8_t *eta_nonce);
 
+/* The header ENVELOPE of a raw chain, and every header's hash: the first half
+ * of validateHeader (ouroboros-consensus/src/Ouroboros/Consensus/
+ * HeaderValidation.hs:413-432), validateEnvelope (:297-344), which the crypto
+ * entries above leave to the caller -- block number, slot, previous hash and
+ * the block type's additional checks of header i against header i - 1, over
+ * the same raw headers (Byron and Shelley-family in one buffer, classified as
+ * by ouro_chain_verify_cbor).  The header hash is the point ChainSync and the
+ * ChainDB ask for next.
+ * header_hash[i] (n x 32):
+ *   TPraos  Blake2b-256 of the #6.24 payload, the [header_body, kes_sig] item
+ *           as it stands (ouroboros-consensus-shelley/src/Ouroboros/Consensus/
+ *           Shelley/Ledger/Block.hs:106,142);
+ *   Byron   Blake2b-256(0x82, kind, header item), kind 1 regular / 0 epoch
+ *           boundary, in all three wire forms (ouroboros-consensus-byron/src/
+ *           Ouroboros/Consensus/Byron/Ledger/Block.hs:74, Orphans.hs:101).
+ * envelope[i]: OURO_ENV_* bits of header i on top of header i - 1 AS GIVEN
+ * (header 0 on top of tip_in, NULL = Origin); OURO_ENV_ALL_OK on every header
+ * of a prefix = validateEnvelope accepts that prefix.  All four bits are
+ * evaluated, where the reference stops at the first failure.
+ *   BLOCKNO  0 at Origin, else succ; unchanged from a Byron non-EBB to a Byron
+ *            EBB (Byron/Ledger/HeaderValidation.hs:46-50); succ across eras
+ *            (HardFork/Combinator/Block.hs:235-238).
+ *   SLOT     slot >= 0 at Origin, else >= succ; >= the same slot from a Byron
+ *            EBB to a Byron non-EBB (:52-56); succ across eras (:249-252).
+ *   PREVHASH checkPrevHash' (HeaderValidation.hs:313-318): GenesisHash at
+ *            Origin, else a block hash equal to header i - 1's header_hash.
+ *            TPraos field 2: null = GenesisHash, bytes(32) = a block hash,
+ *            anything else clears the bit.  A Byron EBB of epoch 0 has
+ *            GenesisHash, every other Byron header a block hash.
+ *   EXTRA    Byron: an EBB's slot is a multiple of byron_epoch_slots
+ *            (:61-72).  TPraos with cfg->has_limits: header size (the payload's
+ *            bytes) <= max_header_size, body field 7 <= max_body_size, field
+ *            13 <= max_major_pv (ledger-specs chainChecks, called at
+ *            Shelley/Ledger/Ledger.hs:395-396).  Otherwise set.
+ * Slots: TPraos field 1; Byron epoch * byron_epoch_slots + slot in epoch
+ * (an EBB: epoch * byron_epoch_slots), Word64 arithmetic.
+ * status[i]: the slicer's OURO_PACK_* of the header's era, as
+ * ouro_chain_verify_cbor reports it.  A header that did not slice, or whose
+ * envelope fields have another shape (an EBB is accepted by the slicer
+ * without a look inside), has envelope 0 and a zero hash; its successor has
+ * the three link bits clear and its own EXTRA bit evaluated.
+ * tip_out (optional): the last header as a tip, so that calls chain: passing
+ * it as the next call's tip_in gives the bits one call over both batches
+ * gives.  (After an unusable last header its proto is 0xff: nothing links.)
+ * OURO_EINVAL before anything runs: NULL raw / off / len / cfg / status /
+ * header_hash / envelope with n > 0, a span outside raw_bytes, a tip_in with
+ * origin set and another field nonzero (or proto / is_ebb out of range), and
+ * byron_epoch_slots == 0 when a header of the batch is PBFT.
+ * How it runs: one upload, the envelope slicer (both eras' slicers without
+ * their rows), the hash kernel (one lane per header) and the link kernel on
+ * the calling thread's stream, one copy back; a device error recomputes on
+ * the host path.  _host: the host path alone.  _device: raw / off / len /
+ * status / header_hash / envelope / tip_out are device pointers (tip_out may
+ * be NULL), cfg and tip_in host pointers read before the call returns; raw
+ * 4-byte aligned and its allocation extended to the next multiple of 4, as
+ * for ouro_block_integrity_verify_cbor_device; header_hash 16-byte aligned and
+ * tip_out 8-byte aligned (OURO_EINVAL otherwise); work >=
+ * ouro_chain_envelope_work_bytes(n) of device memory; enqueued on `stream`,
+ * not synchronised; a span outside raw_bytes is status OURO_PACK_ESPAN, and
+ * with byron_epoch_slots == 0 a PBFT header is unusable (envelope 0).
+ * n == 0: cfg and tip_in are checked all the same; the host-buffer forms then
+ * write tip_in's tip to tip_out, the device form writes nothing. */
+#define OURO_ENV_BLOCKNO_OK 0x01u
+#define OURO_ENV_SLOT_OK 0x02u
+#define OURO_ENV_PREVHASH_OK 0x04u
+#define OURO_ENV_EXTRA_OK 0x08u
+#define OURO_ENV_ALL_OK 0x0fu
+typedef struct ouro_chain_tip {
+  uint8_t origin; /* 1 = no header yet; every other field then 0 */
+  uint8_t proto;  /* OURO_PROTO_* of the tip's header                */
+  uint8_t is_ebb;
+  uint8_t reserved[5];
+  uint64_t slot;
+  uint64_t block_no;
+  uint8_t hash[32];
+} ouro_chain_tip;
+typedef struct ouro_envelope_cfg {
+  uint64_t byron_epoch_slots; /* slots of a Byron epoch (mainnet: 21600)  */
+  uint64_t has_limits;        /* nonzero: the three TPraos limits apply  */
+  uint64_t max_header_size;
+  uint64_t max_body_size;
+  uint64_t max_major_pv;
+} ouro_envelope_cfg;
+int ouro_chain_envelope_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                             const uint32_t *len, size_t n, const ouro_envelope_cfg *cfg,
+                             const ouro_chain_tip *tip_in, uint8_t *status,
+                             uint8_t *header_hash, uint8_t *envelope, ouro_chain_tip *tip_out);
+int ouro_chain_envelope_cbor_host(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                  const uint32_t *len, size_t n, const ouro_envelope_cfg *cfg,
+                                  const ouro_chain_tip *tip_in, uint8_t *status,
+                                  uint8_t *header_hash, uint8_t *envelope,
+                                  ouro_chain_tip *tip_out);
+size_t ouro_chain_envelope_work_bytes(size_t n);
+int ouro_chain_envelope_cbor_device(void *stream, const uint8_t *raw, size_t raw_bytes,
+                                    const uint64_t *off, const uint32_t *len, size_t n,
+                                    const ouro_envelope_cfg *cfg, const ouro_chain_tip *tip_in,
+                                    void *work, size_t work_bytes, uint8_t *status,
+                                    uint8_t *header_hash, uint8_t *envelope,
+                                    ouro_chain_tip *tip_out);
+
+/* validateHeader (HeaderValidation.hs:413-432) over a raw chain in ONE call:
+ * everything ouro_chain_verify_cbor returns (the arguments up to eta_nonce
+ * are its arguments, with the same meaning, checks and results) and the
+ * envelope of ouro_chain_envelope_cbor (cfg, tip_in, header_hash, envelope,
+ * tip_out as there; header_hash and envelope required).  The longest prefix
+ * with OURO_ENV_ALL_OK and OURO_CHAIN_VALID on every header is what the
+ * reference's sequential fold accepts.
+ * How it runs: the pipeline of ouro_chain_verify_cbor, unchanged; after a
+ * chunk's slicers and kernels, on the same stream and over the bytes already
+ * uploaded, the envelope slicer, the hash kernel and the link kernel run over
+ * the chunk in the caller's order (a mixed chunk keeps a second, caller-order
+ * offset list for them), and the chunk copies back 33 more bytes per header
+ * and its first and last record.  Chunks drain in order: the host links each
+ * chunk's first header to the last record of the chunk before it (or to
+ * tip_in) with the same envelope_link the kernel runs.  A device error
+ * recomputes the batch, envelope included, on the host path.  _host: the host
+ * path alone.  byron_epoch_slots == 0 with a PBFT header in the batch is
+ * OURO_EINVAL before anything runs.  Out of scope: a _multi form (the link
+ * across shards), device pointers, the latency plans, OCERT counter
+ * monotonicity (ledger state). */
+int ouro_chain_validate_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                             const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
+                             int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+                             const uint8_t *eta_alpha, const uint8_t *leader_alpha,
+                             const ouro_envelope_cfg *cfg, const ouro_chain_tip *tip_in,
+                             uint8_t *proto, uint8_t *status, uint8_t *verdict,
+                             uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce,
+                             uint8_t *header_hash, uint8_t *envelope, ouro_chain_tip *tip_out);
+int ouro_chain_validate_cbor_host(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                  const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
+                                  int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+                                  const uint8_t *eta_alpha, const uint8_t *leader_alpha,
+                                  const ouro_envelope_cfg *cfg, const ouro_chain_tip *tip_in,
+                                  uint8_t *proto, uint8_t *status, uint8_t *verdict,
+                                  uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce,
+                                  uint8_t *header_hash, uint8_t *envelope,
+                                  ouro_chain_tip *tip_out);
+
 /* (How ouro_byron_verify_cbor runs, since round 6: on the raw-CBOR pipeline
  * of ouro_tpraos_verify_cbor -- chunks gathered into pinned NUMA-local
  * staging, the device Byron slicer (the same cbor_byron.h parse as

@@ -39,6 +39,12 @@ BLK_KES_OK = 0x01      # ouro_block_integrity_verify_cbor: verifyHeaderIntegrity
 BLK_BODY_OK = 0x02     # blockMatchesHeader
 BLK_ALL_OK = 0x03      # verifyBlockIntegrity
 
+ENV_BLOCKNO_OK = 0x01  # ouro_chain_envelope_cbor envelope[i]
+ENV_SLOT_OK = 0x02
+ENV_PREVHASH_OK = 0x04
+ENV_EXTRA_OK = 0x08
+ENV_ALL_OK = 0x0F
+
 PROTO_PBFT = 0     # ouro_chain_verify_cbor proto[i]: a Byron header
 PROTO_TPRAOS = 1   # a Shelley-family header (and anything unreadable)
 EPOCHS_MAX = 4096  # OURO_EPOCHS_MAX
@@ -100,6 +106,22 @@ class ByronBatch(ctypes.Structure):
                                        "delegate_vk", "magic")]
 
 
+class ChainTip(ctypes.Structure):
+    """Mirror of ``ouro_chain_tip`` (include/ouro_verify.h)."""
+
+    _fields_ = [("origin", ctypes.c_uint8), ("proto", ctypes.c_uint8), ("is_ebb", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 5), ("slot", ctypes.c_uint64),
+                ("block_no", ctypes.c_uint64), ("hash", ctypes.c_uint8 * 32)]
+
+
+class EnvelopeCfg(ctypes.Structure):
+    """Mirror of ``ouro_envelope_cfg`` (include/ouro_verify.h)."""
+
+    _fields_ = [(f, ctypes.c_uint64) for f in ("byron_epoch_slots", "has_limits",
+                                               "max_header_size", "max_body_size",
+                                               "max_major_pv")]
+
+
 # every symbol include/ouro_verify.h (the boundary) and include/ouro_verify_debug.h
 # (diagnostics) declare, with its ctypes signature
 _P = ctypes.c_void_p
@@ -143,6 +165,25 @@ SIGNATURES = {
     "ouro_chain_verify_cbor_multi": (_I, [_P, _I, _P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
                                           ctypes.c_int64, ctypes.POINTER(EpochNonces), _P, _P, _P,
                                           _P, _P, _P, _P, _P]),
+    "ouro_chain_envelope_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.POINTER(EnvelopeCfg),
+                                      ctypes.POINTER(ChainTip), _P, _P, _P,
+                                      ctypes.POINTER(ChainTip)]),
+    "ouro_chain_envelope_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.POINTER(EnvelopeCfg),
+                                           ctypes.POINTER(ChainTip), _P, _P, _P,
+                                           ctypes.POINTER(ChainTip)]),
+    "ouro_chain_envelope_work_bytes": (_SZ, [_SZ]),
+    "ouro_chain_validate_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64,
+                                      ctypes.POINTER(EpochNonces), _P, _P,
+                                      ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip), _P, _P,
+                                      _P, _P, _P, _P, _P, _P, ctypes.POINTER(ChainTip)]),
+    "ouro_chain_validate_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64,
+                                           ctypes.POINTER(EpochNonces), _P, _P,
+                                           ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip),
+                                           _P, _P, _P, _P, _P, _P, _P, _P,
+                                           ctypes.POINTER(ChainTip)]),
+    "ouro_chain_envelope_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ,
+                                             ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip),
+                                             _P, _SZ, _P, _P, _P, _P]),
     "ouro_debug_contexts": (_I, [_I, _P, _P]),
     "ouro_debug_lat_stamps": (_I, [_P]),
     "ouro_debug_clock_stamps": (_I, [_P, _I]),

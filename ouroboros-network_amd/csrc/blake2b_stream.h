@@ -145,6 +145,58 @@ OURO_HD inline void blake2b256_stream(uint32_t out[8], const uint8_t* msg, uint3
   }
 }
 
+// out = Blake2b-256(pre ‖ msg[0 .. len)): npre <= 2 prefix bytes (pre: the
+// first in bits 0..7, the second in bits 8..15) in front of a span, the header
+// hash of a Byron header (envelope.h: 0x82, kind, then the header item).
+// Block b of the hashed message covers the span's bytes
+// [128 b - npre, 128 b + 128 - npre): the first block loads its 128 - npre
+// span bytes (or fewer) as any other block does and shifts the prefix in;
+// every later block is a plain load from a span address.  Each load is
+// b2b_load_block over a piece of the span, so its rule -- every dword read
+// holds at least one byte of the span -- holds here as it does there
+// (tests/test_devcode_prefixed_blake2b.py drives b2b_prefixed_with through
+// b2b_load_dwords and a loader that checks it).  len + npre < 2^32.
+// load(m, p, take): m <- the `take` <= 128 bytes at p, zero padded.
+template <class LoadBlock>
+OURO_FI void b2b_prefixed_with(uint32_t out[8], uint32_t pre, uint32_t npre, const uint8_t* msg,
+                               uint32_t len, LoadBlock load) {
+  uint64_t h[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) h[i] = kB2bIV[i];
+  h[0] ^= 0x01010000ULL ^ 32;
+  const uint8_t* p = msg;
+  uint32_t left = len + npre, skip = npre;
+  uint64_t t = 0;
+  for (;;) {
+    const bool last = left <= 128;
+    const uint32_t blk = last ? left : 128u, take = blk - skip;
+    uint64_t m[16];
+    load(m, p, take);
+    if (skip) {  // the first block: the span's bytes move up behind the prefix
+      const uint32_t sh = 8 * skip;
+#pragma unroll
+      for (int i = 15; i > 0; i--) m[i] = (m[i] << sh) | (m[i - 1] >> (64 - sh));
+      m[0] = (m[0] << sh) | (uint64_t)(pre & ((1u << sh) - 1u));
+    }
+    t += blk;
+    b2b_compress(h, m, t, last);
+    if (last) break;
+    p += take;
+    left -= blk;
+    skip = 0;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    out[2 * i] = (uint32_t)h[i];
+    out[2 * i + 1] = (uint32_t)(h[i] >> 32);
+  }
+}
+OURO_HD inline void blake2b256_stream_prefixed(uint32_t out[8], uint32_t pre, uint32_t npre,
+                                               const uint8_t* msg, uint32_t len) {
+  b2b_prefixed_with(out, pre, npre, msg, len,
+                    [](uint64_t m[16], const uint8_t* p, uint32_t take) { b2b_load_block(m, p, take); });
+}
+
 // Blake2b-256 of 96 bytes held as 24 little-endian words: one final
 // compression with t = 96 (the block body hash over its three segment digests)
 OURO_FI void blake2b256_96(uint32_t out[8], const uint32_t in[24]) {

@@ -16,6 +16,7 @@
 #else  // a plain C++ build of the host slicer (the ASan/UBSan test library)
 #define OURO_HD
 #endif
+#include "envelope.h"
 
 namespace ouro {
 namespace cbor {
@@ -260,10 +261,15 @@ OURO_HD inline uint32_t kes_t_of(uint64_t slot, uint64_t spkp, uint64_t c0) {
 // field 8 (bodyHash), or null.  Shared by the header slicer (pack_one, after
 // it has unwrapped the tag-24 payload) and the block slicer (cbor_block.h,
 // item 0 of a block); `c` bounds every read.
+// er (optional): the header's envelope record (envelope.h), filled for an
+// accepted header from fields 0, 1, 2, 7, 13 and the item's span; it never
+// changes the status.  kRows = false: the acceptance and `er` alone, no row
+// of `o` is touched (the envelope-only entries).
 constexpr uint64_t kAnyEnd = ~0ull;
+template <bool kRows = true>
 OURO_HD inline uint8_t pack_fields(const Cur& c, uint64_t k, uint64_t base, uint64_t era,
                                    uint64_t spkp, const Out& o, size_t i, uint64_t must_end,
-                                   uint64_t* end, uint64_t* field8) {
+                                   uint64_t* end, uint64_t* field8, env::Rec* er = nullptr) {
   int mt;
   uint64_t arg, j;
   bool ind;
@@ -301,22 +307,48 @@ OURO_HD inline uint8_t pack_fields(const Cur& c, uint64_t k, uint64_t base, uint
   const int r7 = bytes_at(c, fs[12], 64, &sg), r8 = bytes_at(c, ts[1], 448, &ks);
   if (r7 == kBytesShape || r8 == kBytesShape) return OURO_PACK_ESHAPE;
   if (r0 | r1 | r2 | r3 | r4 | r5 | r6 | r7 | r8) return OURO_PACK_ESIZE;
-  copy_bytes(o.issuer_vk + 32 * i, ivk, 32);
-  copy_bytes(o.vrf_vk + 32 * i, vvk, 32);
-  copy_bytes(o.eta_output + 64 * i, eo, 64);
-  copy_bytes(o.eta_proof + 80 * i, ep, 80);
-  copy_bytes(o.leader_output + 64 * i, lo, 64);
-  copy_bytes(o.leader_proof + 80 * i, lp, 80);
-  copy_bytes(o.hot_vk + 32 * i, hvk, 32);
-  copy_bytes(o.sigma + 64 * i, sg, 64);
-  copy_bytes(o.kes_sig + 448 * i, ks, 448);
-  o.counter[i] = counter;
-  o.c0[i] = c0;
-  o.kes_t[i] = kes_t_of(slot, spkp, c0);
-  o.body_off[i] = base + ts[0];
-  o.body_len[i] = (uint32_t)(te[0] - ts[0]);
-  if (o.slot) o.slot[i] = slot;
-  if (o.era) o.era[i] = (uint8_t)(era > 255 ? 255 : era);
+  if (er) {
+    env::rec_clear(er);
+    er->sliced = 1;
+    er->proto = OURO_PROTO_TPRAOS;
+    er->slot = slot;
+    er->block_no = block_no;
+    // field 2: null = GenesisHash, bytes(32) = BlockHash, anything else neither
+    const uint8_t* ph;
+    if (fe[2] - fs[2] == 1 && cb(c, fs[2]) == 0xf6) {
+      er->prev_kind = env::kPrevGenesis;
+    } else if (bytes_at(c, fs[2], 32, &ph) == kBytesOk) {
+      er->prev_kind = env::kPrevBlock;
+      const uint64_t p0 = (uint64_t)(ph - c.b);
+      for (int q = 0; q < 32; q++) er->prev_hash[q] = (uint8_t)cb(c, p0 + q);
+    } else {
+      er->prev_kind = env::kPrevBad;
+    }
+    uint64_t bsz = 0, pv = 0;
+    er->limits_ok = uint_at(c, fs[7], &bsz) && uint_at(c, fs[13], &pv);
+    er->body_size = er->limits_ok ? bsz : 0;
+    er->prot_major = er->limits_ok ? pv : 0;
+    er->hdr_off = base + k;
+    er->hdr_len = er->header_size = (uint32_t)(te[1] - k);
+  }
+  if (kRows) {
+    copy_bytes(o.issuer_vk + 32 * i, ivk, 32);
+    copy_bytes(o.vrf_vk + 32 * i, vvk, 32);
+    copy_bytes(o.eta_output + 64 * i, eo, 64);
+    copy_bytes(o.eta_proof + 80 * i, ep, 80);
+    copy_bytes(o.leader_output + 64 * i, lo, 64);
+    copy_bytes(o.leader_proof + 80 * i, lp, 80);
+    copy_bytes(o.hot_vk + 32 * i, hvk, 32);
+    copy_bytes(o.sigma + 64 * i, sg, 64);
+    copy_bytes(o.kes_sig + 448 * i, ks, 448);
+    o.counter[i] = counter;
+    o.c0[i] = c0;
+    o.kes_t[i] = kes_t_of(slot, spkp, c0);
+    o.body_off[i] = base + ts[0];
+    o.body_len[i] = (uint32_t)(te[0] - ts[0]);
+    if (o.slot) o.slot[i] = slot;
+    if (o.era) o.era[i] = (uint8_t)(era > 255 ? 255 : era);
+  }
   if (end) *end = te[1];
   if (field8) *field8 = fs[8];
   return OURO_PACK_OK;
@@ -328,8 +360,9 @@ OURO_HD inline uint8_t pack_fields(const Cur& c, uint64_t k, uint64_t base, uint
 // the [header_body, kes_sig] item is parsed from its payload ALONE and must
 // end exactly where the payload ends ("trailing bytes in CBOR-in-CBOR"), and
 // nothing may follow the header inside its span.
+template <bool kRows = true>
 OURO_HD inline uint8_t pack_one(const uint8_t* raw, uint64_t base, uint32_t len, uint64_t spkp, const Out& o,
-                 size_t i) {
+                 size_t i, env::Rec* er = nullptr) {
   const Cur outer{raw + base, len};
   int mt;
   uint64_t arg, j, pos = 0, era = 1;
@@ -348,7 +381,7 @@ OURO_HD inline uint8_t pack_one(const uint8_t* raw, uint64_t base, uint32_t len,
   if (outer.n - k < arg) return OURO_PACK_ECBOR;       // payload past the span
   if (k + arg != outer.n) return OURO_PACK_ECBOR;      // bytes after the header
   const Cur c{raw + base, k + arg};                    // the payload's end bounds the parse
-  return pack_fields(c, k, base, era, spkp, o, i, c.n, nullptr, nullptr);
+  return pack_fields<kRows>(c, k, base, era, spkp, o, i, c.n, nullptr, nullptr, er);
 }
 
 OURO_HD inline void zero_row(const Out& o, size_t i) {

@@ -74,9 +74,53 @@ OURO_HD inline bool uint_le(const Cur& c, uint64_t i, uint64_t max, uint64_t* v)
   return uint_at(c, i, v) && *v <= max;
 }
 
+// The envelope record (envelope.h) of the accepted Byron header whose item
+// starts at h and ends at c.n.  Regular: slot = epoch * epoch_slots + the
+// slot inside the epoch (slotId), block_no = the one uint of `difficulty`,
+// prevHash always a block hash.  Epoch boundary: [magic, prevHash, bodyProof,
+// [epoch, [difficulty]], extra], slot = epoch * epoch_slots, and the previous
+// hash is GenesisHash iff epoch is 0 (cardano-ledger's boundary-header
+// decoder, reached through ouroboros-consensus-byron/src/Ouroboros/Consensus/
+// Byron/Ledger/Block.hs:221-227).  Slots are Word64 arithmetic.  Fields of
+// another shape leave the record cleared (unusable); the status is the
+// slicer's alone.  slot_at / diff_at: the slotId (or the EBB's epoch) and
+// difficulty items, prev_at: the prevHash item.
+OURO_HD inline void byron_env(const Cur& c, uint64_t base, uint64_t h, bool ebb, uint64_t prev_at,
+                              uint64_t slot_at, uint64_t diff_at, uint64_t epoch_slots,
+                              env::Rec* er) {
+  env::rec_clear(er);
+  uint64_t s[2], e[2], epoch, in_epoch = 0, diff;
+  if (ebb) {
+    if (!uint_at(c, slot_at, &epoch)) return;
+  } else {
+    if (fixed_array(c, slot_at, s, e, 2)) return;
+    if (!uint_at(c, s[0], &epoch) || !uint_at(c, s[1], &in_epoch)) return;
+  }
+  if (fixed_array(c, diff_at, s, e, 1) || !uint_at(c, s[0], &diff)) return;
+  const uint8_t* ph;
+  if (bytes_at(c, prev_at, 32, &ph) != kBytesOk) return;
+  er->sliced = 1;
+  er->proto = OURO_PROTO_PBFT;
+  er->is_ebb = ebb ? 1 : 0;
+  er->slot = epoch * epoch_slots + in_epoch;
+  er->block_no = diff;
+  er->prev_kind = (ebb && epoch == 0) ? env::kPrevGenesis : env::kPrevBlock;
+  if (er->prev_kind == env::kPrevBlock) {
+    const uint64_t p0 = (uint64_t)(ph - c.b);
+    for (int q = 0; q < 32; q++) er->prev_hash[q] = (uint8_t)cb(c, p0 + q);
+  }
+  er->hdr_off = base + h;
+  er->hdr_len = (uint32_t)(c.n - h);
+}
+
 // magic_cfg: the configured ProtocolMagicId, or -1 for each header's own
+// er (optional): the header's envelope record, for a regular header and for
+// an epoch-boundary one (whose fields only this looks at); epoch_slots: the
+// slots of a Byron epoch.  kRows = false: the acceptance and `er` alone.
+template <bool kRows = true>
 OURO_HD inline uint8_t byron_pack_one(const uint8_t* raw, uint64_t base, uint32_t len,
-                                      int64_t magic_cfg, const ByronOut& o, size_t i) {
+                                      int64_t magic_cfg, const ByronOut& o, size_t i,
+                                      env::Rec* er = nullptr, uint64_t epoch_slots = 0) {
   const Cur outer{raw + base, len};
   int mt;
   uint64_t arg, j, k, pos = 0, kind = 0;
@@ -122,7 +166,14 @@ OURO_HD inline uint8_t byron_pack_one(const uint8_t* raw, uint64_t base, uint32_
   if (kind == 0) {  // no signature; its fields are not checked
     uint64_t he;
     if (!skip(c, h, &he)) return OURO_PACK_ECBOR;
-    return he == c.n ? OURO_PACK_EBB : OURO_PACK_ECBOR;
+    if (he != c.n) return OURO_PACK_ECBOR;
+    if (er) {
+      if (!fixed_array(c, h, fs, fe, 5) && !fixed_array(c, fs[3], bs, be, 2))
+        byron_env(c, base, h, true, fs[1], bs[0], bs[1], epoch_slots, er);
+      else
+        env::rec_clear(er);
+    }
+    return OURO_PACK_EBB;
   }
   // one walk of the header's five fields; it must end where the payload does
   if ((st = fixed_array(c, h, fs, fe, 5))) return st;
@@ -140,6 +191,8 @@ OURO_HD inline uint8_t byron_pack_one(const uint8_t* raw, uint64_t base, uint32_
             r2 = bytes_at(c, is[1], 64, &sg);
   if (r0 == kBytesShape || r1 == kBytesShape || r2 == kBytesShape) return OURO_PACK_ESHAPE;
   if (r0 | r1 | r2) return OURO_PACK_ESIZE;
+  if (er) byron_env(c, base, h, false, fs[1], cs[0], cs[2], epoch_slots, er);
+  if (!kRows) return OURO_PACK_OK;
   const uint64_t m = magic_cfg < 0 ? magic : (uint64_t)magic_cfg;
   uint8_t* d = o.msg + o.msg_off[i];
   uint64_t n = 0;

@@ -237,6 +237,44 @@ int dh_blake2b256_dwords(uint8_t* out, const uint8_t* msg, uint32_t len) {
   memcpy(out, h, 32);
   return bad ? -1 : loads;
 }
+// Blake2b-256 of npre <= 2 prefix bytes (pre: the first in bits 0..7) and a
+// span (blake2b_stream.h blake2b256_stream_prefixed): the host build ...
+void dh_blake2b256_prefixed(uint8_t* out, uint32_t pre, uint32_t npre, const uint8_t* msg,
+                            uint32_t len) {
+  uint32_t h[8];
+  blake2b256_stream_prefixed(h, pre, npre, msg, len);
+  memcpy(out, h, 32);
+}
+// ... and the same routine (b2b_prefixed_with) through the DEVICE's block
+// loads with the rule-checking loader of dh_blake2b256_dwords: the number of
+// dwords read, or -1 on the first read that is unaligned or holds no byte of
+// msg[0 .. len).
+int dh_blake2b256_prefixed_dwords(uint8_t* out, uint32_t pre, uint32_t npre, const uint8_t* msg,
+                                  uint32_t len) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(msg), e0 = a0 + len;
+  int loads = 0;
+  bool bad = false;
+  auto ld = [&](uintptr_t x) -> uint32_t {
+    if ((x & 3) || len == 0 || x + 4 <= a0 || x >= e0) {
+      bad = true;
+      return 0xdeadbeefu;
+    }
+    loads++;
+    uint32_t v = 0;  // (bytes outside the span come back as set bits)
+    for (int k = 0; k < 4; k++) {
+      const uintptr_t b = x + (uintptr_t)k;
+      const uint32_t byte = (b >= a0 && b < e0) ? *reinterpret_cast<const uint8_t*>(b) : 0xffu;
+      v |= byte << (8 * k);
+    }
+    return v;
+  };
+  uint32_t h[8];
+  b2b_prefixed_with(h, pre, npre, msg, len, [&](uint64_t m[16], const uint8_t* p, uint32_t take) {
+    b2b_load_dwords(m, reinterpret_cast<uintptr_t>(p), take, ld);
+  });
+  memcpy(out, h, 32);
+  return bad ? -1 : loads;
+}
 void dh_elligator2(uint8_t* out, const uint8_t* r32) {
   uint32_t r[8];
   bytes_to_words8(r, r32);

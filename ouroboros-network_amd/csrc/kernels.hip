@@ -764,6 +764,91 @@ __global__ void __launch_bounds__(kB2bBlock) k_blake2b256(size_t m, const uint8_
   }
 }
 
+// ---- the header envelope (envelope.h; include/ouro_verify.h
+// ouro_chain_envelope_cbor) ----
+// The envelope slicer, one lane per header in the caller's order: the
+// header's era (cbor.h era_class), then that era's slicer WITHOUT its rows
+// (pack_one<false> / byron_pack_one<false>: the same acceptance, so status[i]
+// is what the crypto entries report) filling record i -- fields, previous
+// hash and the span the header hash covers.  A header that is rejected, or
+// whose envelope fields have another shape, keeps a zero record.
+__global__ void __launch_bounds__(kBlock) k_envelope_slice(const uint8_t* __restrict__ raw,
+                                                           size_t raw_bytes,
+                                                           const uint64_t* __restrict__ off,
+                                                           const uint32_t* __restrict__ len,
+                                                           size_t n, uint64_t epoch_slots,
+                                                           env::Rec* __restrict__ rec,
+                                                           uint8_t* __restrict__ status) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n; i += nth) {
+    const uint64_t o0 = off[i];
+    const uint32_t l0 = len[i];
+    env::Rec* r = rec + i;
+    env::rec_clear(r);
+    uint8_t st;
+    if (o0 > raw_bytes || raw_bytes - o0 < l0) {
+      st = (uint8_t)OURO_PACK_ESPAN;
+    } else if (cbor::era_class(raw + o0, l0) == OURO_PROTO_PBFT) {
+      st = cbor::byron_pack_one<false>(raw, o0, l0, -1, cbor::ByronOut{}, i, r, epoch_slots);
+      if (epoch_slots == 0) env::rec_clear(r);  // no Byron slot without the epoch's length
+    } else {
+      st = cbor::pack_one<false>(raw, o0, l0, 1, cbor::Out{}, i, r);
+    }
+    status[i] = st;
+  }
+}
+
+// Record i's header hash, one lane per header (workgroups of one wave, as
+// k_blake2b256): Blake2b-256 of the sliced span behind the era's prefix
+// (blake2b_stream.h blake2b256_stream_prefixed).  raw must be 4-byte aligned.
+// No length-class sort: the headers of one era are within a compression or
+// two of each other.  An unusable record keeps its zero hash.
+__global__ void __launch_bounds__(kB2bBlock) k_header_hash(size_t n,
+                                                           const uint8_t* __restrict__ raw,
+                                                           size_t raw_bytes, env::Rec* rec) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n; i += nth) {
+    env::Rec* r = rec + i;
+    if (!r->sliced) continue;
+    const uint64_t o0 = r->hdr_off;
+    const uint32_t l0 = r->hdr_len;
+    if (o0 > raw_bytes || raw_bytes - o0 < l0) continue;  // (cannot happen: the slicer's span)
+    uint32_t npre;
+    const uint32_t pre = env::hash_prefix(*r, &npre);
+    uint32_t d[8];
+    blake2b256_stream_prefixed(d, pre, npre, raw + o0, l0);
+    stg4(r->hash, make_int4((int)d[0], (int)d[1], (int)d[2], (int)d[3]));
+    stg4(r->hash + 16, make_int4((int)d[4], (int)d[5], (int)d[6], (int)d[7]));
+  }
+}
+
+// envelope[i] = envelope_link(record i - 1, record i) in the caller's order
+// (header 0 on top of `tip`), the hash out of the record, and the last
+// header as the next call's tip.  header_hash: 16-byte aligned.  ends
+// (optional): the first and the last record, for the raw pipeline's host to
+// link a chunk to the one before it (raw_pipe.cpp raw_drain).
+__global__ void __launch_bounds__(kBlock) k_envelope_link(size_t n, const env::Rec* __restrict__ rec,
+                                                          env::Rec tip, ouro_envelope_cfg cfg,
+                                                          uint8_t* __restrict__ envelope,
+                                                          uint8_t* __restrict__ header_hash,
+                                                          ouro_chain_tip* tip_out,
+                                                          env::Rec* __restrict__ ends) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n; i += nth) {
+    const env::Rec cur = rec[i];
+    const env::Rec prev = i ? rec[i - 1] : tip;
+    envelope[i] = env::envelope_link(prev, cur, cfg);
+    stg4(header_hash + 32 * i, ldg4(rec[i].hash));
+    stg4(header_hash + 32 * i + 16, ldg4(rec[i].hash + 16));
+    if (i == n - 1 && tip_out) env::tip_of_rec(tip_out, cur);
+    if (ends && i == 0) ends[0] = cur;
+    if (ends && i == n - 1) ends[1] = cur;
+  }
+}
+
 // bbHash = Blake2b-256 of the block's three segment digests (96 bytes: one
 // final compression with t = 96), compared with the claimed bodyHash and
 // merged with the KES verdict: verdict[i] = OURO_BLK_* bits, 0 (and a zero
@@ -1270,6 +1355,22 @@ int launch_blake2b(hipStream_t st, size_t m, const uint8_t* msg, size_t msg_byte
   const unsigned hblocks = (unsigned)std::min<size_t>((m + kB2bBlock - 1) / kB2bBlock, 1u << 20);
   hipLaunchKernelGGL(k_blake2b256, dim3(hblocks), dim3(kB2bBlock), 0, st, m, msg, msg_bytes, off,
                      len, perm, out);
+  return launch_check();
+}
+// the header envelope of n raw headers on `st`: slicer, hashes, links
+// (rec: n records of device memory, 64-byte aligned)
+int launch_envelope(hipStream_t st, const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                    const uint32_t* len, size_t n, const ouro_envelope_cfg& cfg,
+                    const env::Rec& tip, env::Rec* rec, uint8_t* status, uint8_t* header_hash,
+                    uint8_t* envelope, ouro_chain_tip* tip_out, env::Rec* ends) {
+  if (n == 0) return OURO_OK;
+  const unsigned blocks = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 4096);
+  const unsigned hblocks = (unsigned)std::min<size_t>((n + kB2bBlock - 1) / kB2bBlock, 1u << 20);
+  hipLaunchKernelGGL(k_envelope_slice, dim3(blocks), dim3(kBlock), 0, st, raw, raw_bytes, off, len,
+                     n, cfg.byron_epoch_slots, rec, status);
+  hipLaunchKernelGGL(k_header_hash, dim3(hblocks), dim3(kB2bBlock), 0, st, n, raw, raw_bytes, rec);
+  hipLaunchKernelGGL(k_envelope_link, dim3(blocks), dim3(kBlock), 0, st, n, rec, tip, cfg, envelope,
+                     header_hash, tip_out, ends);
   return launch_check();
 }
 void launch_block_finish(hipStream_t st, unsigned blocks, size_t n, const uint8_t* status,

@@ -89,6 +89,15 @@ int launch_blake2b(hipStream_t st, size_t m, const uint8_t* msg, size_t msg_byte
 void launch_block_finish(hipStream_t st, unsigned blocks, size_t n, const uint8_t* status,
                          const uint8_t* digest, const uint8_t* claimed, const uint8_t* kes,
                          uint8_t* verdict, uint8_t* body_hash);
+// the header envelope (envelope.h): k_envelope_slice, k_header_hash and
+// k_envelope_link over n raw headers; rec: n records, 64-byte aligned; raw
+// 4-byte aligned, header_hash 16-byte aligned (checks its own launches);
+// ends (optional, device): receives the first and the last record
+int launch_envelope(hipStream_t st, const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                    const uint32_t* len, size_t n, const ouro_envelope_cfg& cfg,
+                    const ouro::env::Rec& tip, ouro::env::Rec* rec, uint8_t* status,
+                    uint8_t* header_hash, uint8_t* envelope, ouro_chain_tip* tip_out,
+                    ouro::env::Rec* ends = nullptr);
 void launch_vrf03_proof_to_hash(hipStream_t st, unsigned blocks, size_t n, const uint8_t* proof,
                                 uint8_t* beta, uint8_t* verdict);
 void launch_plan_stage(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst, size_t n16,

@@ -57,6 +57,10 @@ using namespace ouro_rt;
 // era's path above, a mixed chunk both slicers and both kernels on its one
 // upload, each over its own offset / length list (raw_stage, raw_launch), and
 // raw_drain scatters the two result sets back to the caller's order.
+// A validating call (ouro_chain_validate_cbor) is the chain kind with
+// RawCall::env set: behind each chunk's work, on the same stream, the envelope
+// kernels (launches.h launch_envelope) over the chunk in the caller's order;
+// raw_drain links each chunk's first header to the chunk before it.
 namespace {
 constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kRawChunkBytes = (size_t)96 << 20;
@@ -68,8 +72,11 @@ struct RawChunk {
 
 // the pinned / device input block of a chunk of m headers and `bytes` raw bytes
 // (tab: the call's epoch-nonce schedule block, uploaded with every chunk)
+// (eoff / elen, behind everything else: a validating call's mixed chunk keeps
+// the caller-order offset and length lists for the envelope kernels, which
+// link each header to its neighbour in the stream; total_env includes them)
 struct RawIn {
-  size_t off, len, eta0, alpha, tab, raw, total;
+  size_t off, len, eta0, alpha, tab, raw, total, eoff, elen, total_env;
 };
 RawIn raw_in(size_t m, size_t bytes, bool alphas, size_t tab_bytes) {
   RawIn l;
@@ -80,6 +87,9 @@ RawIn raw_in(size_t m, size_t bytes, bool alphas, size_t tab_bytes) {
   l.tab = a16(l.alpha + (alphas ? 64 * m : 0));
   l.raw = l.tab + a16(tab_bytes);
   l.total = l.raw + a16(std::max<size_t>(bytes, 16));
+  l.eoff = l.total;
+  l.elen = l.eoff + a16(8 * m);
+  l.total_env = l.elen + a16(4 * m);
   return l;
 }
 // the Byron results of a mixed chunk (mb PBFT headers), behind the TPraos block
@@ -111,6 +121,24 @@ size_t raw_out_bytes(const RawCall& c, const RawOut& o, size_t m) {
   if (c.bl) return o.nonce;
   if (c.be) return o.bl;
   return o.verdict + m;
+}
+
+// a validating call's envelope block of a chunk: on the device the records,
+// then what is copied back -- hash | bits | the first and the last record --
+// then the envelope slicer's status (not copied: the chain kind's is the same)
+struct RawEnvOut {
+  size_t rec, hash, bits, ends, back, status, total;
+};
+RawEnvOut raw_env_out(size_t m) {
+  RawEnvOut e;
+  e.rec = 0;
+  e.hash = (sizeof(env::Rec) * m + 63) & ~(size_t)63;
+  e.bits = e.hash + 32 * m;
+  e.ends = e.bits + a16(m);
+  e.back = e.ends + 2 * sizeof(env::Rec) - e.hash;
+  e.status = e.ends + 2 * sizeof(env::Rec);
+  e.total = e.status + a16(m);
+  return e;
 }
 
 // Every span inside raw (as ouro_tpraos_pack_cbor demands), and the chunks.
@@ -175,7 +203,8 @@ int raw_stage(RawSlot& s, const RawCall& c, const RawChunk& k, int width) {
   const bool alphas = c.ea != nullptr;
   const bool chain = c.kind == kRawChain;
   const RawIn L = raw_in(k.m, k.bytes, alphas, c.epochs_bytes);
-  int rc = pinned_at_least(&s.h_in, &s.h_in_cap, L.total + L.total / 8);
+  const size_t in_bytes = c.env ? L.total_env : L.total;
+  int rc = pinned_at_least(&s.h_in, &s.h_in_cap, in_bytes + in_bytes / 8);
   if (rc) return rc;
   uint64_t* noff = reinterpret_cast<uint64_t*>(s.h_in + L.off);
   uint64_t at = 0;
@@ -235,6 +264,10 @@ int raw_stage(RawSlot& s, const RawCall& c, const RawChunk& k, int width) {
     o2.resize(k.m);
   } catch (const std::bad_alloc&) {
     return fail(OURO_EDEVICE, "raw CBOR gather: out of host memory");
+  }
+  if (c.env) {  // the caller's order, before the lists are reordered
+    memcpy(s.h_in + L.eoff, noff, 8 * k.m);
+    memcpy(s.h_in + L.elen, c.len + k.lo, 4 * k.m);
   }
   size_t at_t = 0, at_b = mt;
   for (size_t i = 0; i < k.m; i++) {
@@ -316,8 +349,14 @@ int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
                          : c.kind == kRawBlock ? a16(ouro_block_pack_bytes(mt)) + 64
                                                : a16(ouro_tpraos_pack_bytes(mt)) + 64;
   const cbor::ByronLayout bl = cbor::byron_layout(mb, k.bytes + cbor::kByronMsgExtra * mb);
+  const bool env_lists = c.env && s.mode == kModeMixed;
+  const size_t up = env_lists ? L.total_env : L.total;
+  const RawEnvOut EO = raw_env_out(k.m);
   int rc;
-  if ((rc = ensure(s.d_in, L.total)) ||
+  if (c.env && ((rc = ensure(s.d_env, EO.total + 64)) ||
+                (rc = pinned_at_least(&s.h_env, &s.h_env_cap, EO.back))))
+    return rc;
+  if ((rc = ensure(s.d_in, up)) ||
       (rc = ensure(s.d_arena, arena_t + (mb ? bl.total + 64 : 0))) ||
       (rc = ensure(s.d_out, a16(O.total) + (back_b ? OB.total : 0))) ||
       (rc = pinned_at_least(&s.h_out, &s.h_out_cap, a16(back) + back_b)))
@@ -325,7 +364,7 @@ int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
   uint8_t* din = static_cast<uint8_t*>(s.d_in.p);
   uint8_t* dout = static_cast<uint8_t*>(s.d_out.p);
   uint8_t* darena = static_cast<uint8_t*>(s.d_arena.p);
-  OURO_HIP(hipMemcpyAsync(din, s.h_in, L.total, hipMemcpyHostToDevice, s.st));
+  OURO_HIP(hipMemcpyAsync(din, s.h_in, up, hipMemcpyHostToDevice, s.st));
   const uint8_t* draw = din + L.raw;
   const uint64_t* doff = reinterpret_cast<const uint64_t*>(din + L.off);
   const uint32_t* dlen = reinterpret_cast<const uint32_t*>(din + L.len);
@@ -354,6 +393,20 @@ int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
                                      dout + a16(O.total) + OB.verdict)))
       return rc;
   }
+  if (c.env) {
+    // the envelope on the same stream over the bytes already uploaded, in the
+    // caller's order whatever the chunk's era make-up; its first header is
+    // linked on the host when the chunk before it has drained (raw_drain)
+    uint8_t* de = cbor::arena_base(s.d_env.p);
+    const uint64_t* eoff = env_lists ? reinterpret_cast<const uint64_t*>(din + L.eoff) : doff;
+    const uint32_t* elen = env_lists ? reinterpret_cast<const uint32_t*>(din + L.elen) : dlen;
+    if ((rc = launch_envelope(s.st, draw, k.bytes, eoff, elen, k.m, c.env->cfg, c.env->tip,
+                              reinterpret_cast<env::Rec*>(de + EO.rec), de + EO.status,
+                              de + EO.hash, de + EO.bits, nullptr,
+                              reinterpret_cast<env::Rec*>(de + EO.ends))))
+      return rc;
+    OURO_HIP(hipMemcpyAsync(s.h_env, de + EO.hash, EO.back, hipMemcpyDeviceToHost, s.st));
+  }
   OURO_HIP(hipMemcpyAsync(s.h_out, dout, back, hipMemcpyDeviceToHost, s.st));
   if (back_b)
     OURO_HIP(hipMemcpyAsync(s.h_out + a16(back), dout + a16(O.total), back_b,
@@ -370,6 +423,18 @@ int raw_drain(RawSlot& s, const RawCall& c) {
   if (!s.busy) return OURO_OK;
   s.busy = false;
   OURO_HIP(hipEventSynchronize(s.done));
+  if (c.env) {
+    // chunks drain in order: this chunk's first header on top of the last
+    // record of the one before it (or the tip), with the kernels' own rule
+    const RawEnvOut EO = raw_env_out(s.m);
+    const uint8_t* h = s.h_env;  // (the block from its hashes on)
+    memcpy(c.env->hash + 32 * s.lo, h, 32 * s.m);
+    memcpy(c.env->envelope + s.lo, h + (EO.bits - EO.hash), s.m);
+    env::Rec ends[2];
+    memcpy(ends, h + (EO.ends - EO.hash), sizeof ends);
+    c.env->envelope[s.lo] = env::envelope_link(c.env->prev, ends[0], c.env->cfg);
+    c.env->prev = ends[1];
+  }
   const bool hdr = c.kind == kRawHdr || c.kind == kRawChain;
   if (s.mode == kModeMixed) {
     // both result sets back to the caller's order (RawSlot idx: the TPraos
@@ -450,6 +515,7 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
     if (!s.done) OURO_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
   }
   const int width = (int)knob_size(ouro_knobs::get().cbor_copy_threads, 8, 1, 64);
+  if (c.env) c.env->prev = c.env->tip;
   size_t ci = 0;
   for (; ci < chunks.size() && !rc; ci++) {
     RawSlot& s = p.s[ci % S];
@@ -477,6 +543,7 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
   const double total = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
   const double st[6] = {total, gather_ms, wait_ms, (double)chunks.size(), (double)S, (double)width};
   memcpy(t_raw_stats, st, sizeof st);
+  if (!rc && c.env && c.env->tip_out) env::tip_of_rec(c.env->tip_out, c.env->prev);
   return rc;
 }
 
@@ -575,7 +642,14 @@ int raw_host(const RawCall& c) {
   if (c.kind == kRawBlock) return block_host(c);
   if (c.kind == kRawChain) {
     try {  // (its lists are vectors; no exception crosses the C ABI)
-      return raw_host_chain(c);
+      if (int rc = raw_host_chain(c)) return rc;
+      if (!c.env) return OURO_OK;
+      // a validating call: the envelope with the host build of the same routines
+      if (int rc = env_host_run(c.raw, c.off, c.len, c.n, c.env->cfg, c.env->tip, nullptr,
+                                c.env->hash, c.env->envelope, &c.env->prev))
+        return rc;
+      if (c.env->tip_out) env::tip_of_rec(c.env->tip_out, c.env->prev);
+      return OURO_OK;
     } catch (const std::bad_alloc&) {
       return fail(OURO_EDEVICE, "raw CBOR host path: out of host memory");
     }
@@ -751,6 +825,76 @@ int ouro_chain_verify_cbor_host(const uint8_t* raw, size_t raw_bytes, const uint
   if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
                           epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
                           beta_leader, eta_nonce))
+    return rc;
+  return raw_verify_host(a.c);
+}
+
+// validateHeader's two halves over a raw chain in one call (ouroboros-consensus/
+// src/Ouroboros/Consensus/HeaderValidation.hs:413-432): the chain kind's crypto
+// as ouro_chain_verify_cbor runs it, and per chunk, on the same stream and over
+// the bytes already uploaded, the envelope kernels (RawCall env).
+namespace {
+int validate_call(ChainArgs* a, RawEnv* e, const uint8_t* raw, size_t raw_bytes,
+                  const uint64_t* off, const uint32_t* len, size_t n,
+                  const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in,
+                  uint8_t* header_hash, uint8_t* envelope, ouro_chain_tip* tip_out) {
+  if (int rc = env_args(cfg, tip_in, &e->tip)) return rc;
+  if (n == 0) {  // nothing to link: the checked tip passes through
+    if (tip_out) env::tip_of_rec(tip_out, e->tip);
+    return OURO_OK;
+  }
+  if (!header_hash || !envelope) return fail(OURO_EINVAL, "null header_hash or envelope");
+  e->cfg = *cfg;
+  e->prev = e->tip;
+  e->hash = header_hash;
+  e->envelope = envelope;
+  e->tip_out = tip_out;
+  a->c.env = e;
+  for (size_t i = 0; i < n; i++)  // every span before anything runs
+    if (off[i] > raw_bytes || raw_bytes - off[i] < len[i])
+      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
+  if (cfg->byron_epoch_slots == 0) return env_needs_epoch_slots(raw, off, len, n);
+  return OURO_OK;
+}
+}  // namespace
+
+int ouro_chain_validate_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                             const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
+                             int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+                             const uint8_t* eta_alpha, const uint8_t* leader_alpha,
+                             const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in,
+                             uint8_t* proto, uint8_t* status, uint8_t* verdict, uint8_t* beta_eta,
+                             uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+                             uint8_t* envelope, ouro_chain_tip* tip_out) {
+  ChainArgs a;
+  RawEnv e{};
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
+                             envelope, tip_out))
+    return rc;
+  return raw_verify(a.c);
+}
+
+int ouro_chain_validate_cbor_host(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                                  const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
+                                  int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+                                  const uint8_t* eta_alpha, const uint8_t* leader_alpha,
+                                  const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in,
+                                  uint8_t* proto, uint8_t* status, uint8_t* verdict,
+                                  uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce,
+                                  uint8_t* header_hash, uint8_t* envelope,
+                                  ouro_chain_tip* tip_out) {
+  ChainArgs a;
+  RawEnv e{};
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
+                             envelope, tip_out))
     return rc;
   return raw_verify_host(a.c);
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/ouro_verify.h"
+#include "envelope.h"
 #include "launch.h"
 
 // numa.cpp: NUMA placement of a device's host side
@@ -113,6 +114,11 @@ struct RawSlot {
   uint8_t* h_out = nullptr;  // status | verdict | beta_eta | beta_leader | eta_nonce
   size_t h_out_cap = 0;
   Buf d_in, d_arena, d_out;
+  // the envelope of a validating call (RawCall env): the chunk's records, its
+  // hashes | bits | first and last record, and their pinned copy
+  Buf d_env;
+  uint8_t* h_env = nullptr;
+  size_t h_env_cap = 0;
   size_t lo = 0, m = 0;
   bool busy = false;
   // the combined entry (kRawChain): the chunk's era make-up and, for a mixed
@@ -264,6 +270,15 @@ int stage_hdr(Stager& sg, const ouro_tpraos_batch* b, size_t lo, size_t m, Stage
 // (kRawChain: Byron and TPraos headers in one stream, classified per header)
 // (kRawBlock: whole Shelley-family blocks, KES + body hash; block_api.cpp)
 enum RawKind { kRawHdr = 0, kRawKes = 1, kRawByron = 2, kRawChain = 3, kRawBlock = 4 };
+// What a validating call (ouro_chain_validate_cbor) adds to the chain kind:
+// the envelope of every header (envelope.h).  prev: the record the next
+// drained chunk's first header links to (the tip, then each chunk's last).
+struct RawEnv {
+  ouro_envelope_cfg cfg;
+  ouro::env::Rec tip, prev;
+  uint8_t *hash, *envelope;  // OUT: n x 32, n
+  ouro_chain_tip* tip_out;   // OUT, or null
+};
 struct RawCall {
   RawKind kind;
   const uint8_t* raw;
@@ -283,6 +298,7 @@ struct RawCall {
   const uint8_t* epochs = nullptr;
   size_t epochs_bytes = 0;
   uint8_t* body_hash = nullptr;  // block kind: OUT, the computed bbHash (n x 32), or null
+  RawEnv* env = nullptr;         // chain kind: also the header envelope (validate), or null
 };
 int raw_verify(const RawCall& c);
 // block_api.cpp: the block kind's device sequence on one stream (a: the
@@ -291,6 +307,13 @@ int block_launch(hipStream_t st, const uint8_t* draw, size_t raw_bytes, const ui
                  const uint32_t* dlen, size_t n, uint64_t spkp, uint8_t* a, uint8_t* dstatus,
                  uint8_t* dverdict, uint8_t* dbody_hash);
 int block_host(const RawCall& c);
+// envelope_api.cpp: the envelope of n raw host headers on the host path
+// (status may be null); and the checks / conversion of a cfg and a tip
+int env_host_run(const uint8_t* raw, const uint64_t* off, const uint32_t* len, size_t n,
+                 const ouro_envelope_cfg& cfg, const ouro::env::Rec& tip, uint8_t* status,
+                 uint8_t* hash, uint8_t* envelope, ouro::env::Rec* last);
+int env_args(const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in, ouro::env::Rec* tip);
+int env_needs_epoch_slots(const uint8_t* raw, const uint64_t* off, const uint32_t* len, size_t n);
 // the argument checks of a raw call that need no pass over the headers
 int raw_check(const RawCall& c);
 // the same call on the host path alone (ouro_chain_verify_cbor_host)

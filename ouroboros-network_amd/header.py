@@ -588,3 +588,113 @@ def verify_chain_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: in
         _native.check(rc, name)
     out = (proto[:n], status[:n], verdict[:n], be[:n], bl[:n])
     return out + (en[:n],) if nonce else out
+
+
+def _c_tip(tip):
+    """envelope.Tip / None (Origin) -> _native.ChainTip"""
+    from . import _native
+    t = _native.ChainTip()
+    if tip is None:
+        t.origin = 1
+        return t
+    t.proto = tip.proto if tip.usable else 0xFF
+    t.is_ebb = int(bool(tip.is_ebb))
+    t.slot, t.block_no = tip.slot, tip.block_no
+    t.hash[:] = tip.hash
+    return t
+
+
+def _py_tip(t):
+    from . import envelope as E
+    if t.origin:
+        return E.ORIGIN
+    return E.Tip(t.proto, bool(t.is_ebb), t.slot, t.block_no, bytes(t.hash),
+                 usable=t.proto != 0xFF)
+
+
+def _c_cfg(cfg):
+    from . import _native
+    c = _native.EnvelopeCfg()
+    c.byron_epoch_slots = cfg.byron_epoch_slots
+    if cfg.limits is not None:
+        c.has_limits = 1
+        c.max_header_size, c.max_body_size, c.max_major_pv = cfg.limits
+    return c
+
+
+def chain_envelope_cbor(raw_headers, cfg=None, tip=None, *, host: bool = False):
+    """The header envelope of a raw chain and every header's hash (include/
+    ouro_verify.h ouro_chain_envelope_cbor): validateEnvelope of header i on
+    top of header i - 1 as given, header 0 on top of `tip` (an envelope.Tip;
+    None = Origin), under `cfg` (an envelope.Cfg).  host=True: the library's
+    host path, no device.  Returns (status, header_hash (n, 32), envelope,
+    tip_out): the slicer's OURO_PACK_* status, the hashes, the ENV_* bits, and
+    the last header as the next call's tip."""
+    import ctypes
+
+    from . import _native
+    from . import envelope as E
+    buf, off, ln = raw_triplet(raw_headers)
+    n = int(off.size)
+    if ln.size != n:
+        raise ValueError("off / len: one entry per header")
+    m = max(n, 1)
+    status = np.zeros(m, np.uint8)
+    hh = np.zeros((m, 32), np.uint8)
+    bits = np.zeros(m, np.uint8)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    c_cfg, t_in, t_out = _c_cfg(cfg or E.Cfg()), _c_tip(tip), _native.ChainTip()
+    lib = _native.load()
+    name = "ouro_chain_envelope_cbor_host" if host else "ouro_chain_envelope_cbor"
+    rc = getattr(lib, name)(ptr(buf), buf.size, ptr(off), ptr(ln), n, ctypes.byref(c_cfg),
+                            ctypes.byref(t_in), ptr(status), ptr(hh), ptr(bits),
+                            ctypes.byref(t_out))
+    _native.check(rc, name)
+    return status[:n], hh[:n], bits[:n], _py_tip(t_out)
+
+
+def validate_chain_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: int, *,
+                        cfg=None, tip=None, epochs: Optional[EpochNonces] = None,
+                        eta_alpha: Optional[np.ndarray] = None,
+                        leader_alpha: Optional[np.ndarray] = None, nonce: bool = False,
+                        host: bool = False):
+    """validateHeader over a raw chain in one call (include/ouro_verify.h
+    ouro_chain_validate_cbor): verify_chain_cbor's crypto verdicts and
+    chain_envelope_cbor's envelope from one pass of the raw-CBOR pipeline.
+    Returns (crypto, header_hash, envelope, tip_out, accepted): crypto =
+    verify_chain_cbor's tuple; accepted = the length of the longest prefix the
+    reference's sequential fold accepts (every ENV_* bit set and the header
+    valid under its protocol)."""
+    import ctypes
+
+    from . import _native
+    from . import envelope as E
+    buf, off, ln = raw_triplet(raw_headers)
+    n = int(off.size)
+    if ln.size != n:
+        raise ValueError("off / len: one entry per header")
+    m = max(n, 1)
+    proto, status, verdict = (np.zeros(m, np.uint8) for _ in range(3))
+    be = np.zeros((m, 64), np.uint8)
+    bl = np.zeros((m, 64), np.uint8)
+    en = np.zeros((m, 32), np.uint8) if nonce else None
+    hh = np.zeros((m, 32), np.uint8)
+    bits = np.zeros(m, np.uint8)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    ea = None if eta_alpha is None else np.ascontiguousarray(eta_alpha, np.uint8).reshape(n, 32)
+    la = None if leader_alpha is None else \
+        np.ascontiguousarray(leader_alpha, np.uint8).reshape(n, 32)
+    e = None if epochs is None else ctypes.byref(epochs.c_struct())
+    c_cfg, t_in, t_out = _c_cfg(cfg or E.Cfg()), _c_tip(tip), _native.ChainTip()
+    lib = _native.load()
+    name = "ouro_chain_validate_cbor_host" if host else "ouro_chain_validate_cbor"
+    rc = getattr(lib, name)(ptr(buf), buf.size, ptr(off), ptr(ln), n, slots_per_kes_period,
+                            protocol_magic, e, ptr(ea), ptr(la), ctypes.byref(c_cfg),
+                            ctypes.byref(t_in), ptr(proto), ptr(status), ptr(verdict), ptr(be),
+                            ptr(bl), ptr(en), ptr(hh), ptr(bits), ctypes.byref(t_out))
+    _native.check(rc, name)
+    crypto = (proto[:n], status[:n], verdict[:n], be[:n], bl[:n])
+    if nonce:
+        crypto += (en[:n],)
+    valid = np.where(proto[:n] == PROTO_PBFT, verdict[:n] == 1, (verdict[:n] & 0x0F) == 0x0F)
+    return crypto, hh[:n], bits[:n], _py_tip(t_out), E.first_invalid(bits[:n], valid)
