@@ -765,8 +765,9 @@ int ouro_chain_envelope_cbor_device(void *stream, const uint8_t *raw, size_t raw
  * recomputes the batch, envelope included, on the host path.  _host: the host
  * path alone.  byron_epoch_slots == 0 with a PBFT header in the batch is
  * OURO_EINVAL before anything runs.  Out of scope: a _multi form (the link
- * across shards), device pointers, the latency plans, OCERT counter
- * monotonicity (ledger state). */
+ * across shards), device pointers, the latency plans.  The checks that need
+ * the ledger view (pool stake, VRF key hash, leader value, OCERT period and
+ * counter): ouro_chain_validate_ledger_cbor below. */
 int ouro_chain_validate_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
                              const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
                              int64_t protocol_magic, const ouro_epoch_nonces *epochs,
@@ -784,6 +785,169 @@ int ouro_chain_validate_cbor_host(const uint8_t *raw, size_t raw_bytes, const ui
                                   uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce,
                                   uint8_t *header_hash, uint8_t *envelope,
                                   ouro_chain_tip *tip_out);
+
+/* ------------------------------------------- ledger-view header checks ----- */
+/* What SL.updateChainDepState (ouroboros-consensus-shelley/src/Ouroboros/
+ * Consensus/Shelley/Protocol.hs:433-442) checks with the epoch's LedgerView
+ * beside the signatures: the ledger-specs OVERLAY and OCERT rules, per TPraos
+ * header, as OURO_LV_* bits -- all of them, where the reference stops at the
+ * first failure (the OURO_ENV_* convention).  A PBFT or unsliced header gets 0.
+ *   POOL_KNOWN      hashKey (Blake2b-224) of the cold key is in the entry's
+ *                   pool distribution                      (VRFKeyUnknown)
+ *   VRF_KEY_OK      hashVerKeyVRF (Blake2b-256) of the header's VRF key is the
+ *                   registered one                         (VRFKeyWrongVRFKey)
+ *   LEADER_OK       checkLeaderValue of the header's CLAIMED leader output
+ *                   (Protocol.hs:484-485) under that pool's relative stake
+ *                                                          (VRFLeaderValueTooBig)
+ *   KES_PERIOD_OK   c0 <= kesPeriod(slot) < c0 + max_kes_evo, the sum taken
+ *                   without wrapping: c0 > 2^64 - max_kes_evo fails
+ *                                    (KESBeforeStartOCERT, KESAfterEndOCERT)
+ *   COUNTER_OK      the certificate counter does not go back for the pool
+ *                   (CounterTooSmallOCERT): ouro_ocert_counter_fold
+ *   OVERLAY         the slot is an overlay slot (ledger-specs isOverlaySlot:
+ *                   ceil(s d) < ceil((s + 1) d), s = slot - the entry's
+ *                   first_slot, exact integers; d_num == 0: never).  Then only
+ *                   KES_PERIOD_OK is evaluated: the genesis-delegate branch
+ *                   (pbftVrfChecks) stays with the caller.
+ *   BADARG          the leader check's arguments are outside its domain
+ *                   (OURO_LEADER_BADARG); LEADER_OK is then clear. */
+#define OURO_LV_POOL_KNOWN 0x01u
+#define OURO_LV_VRF_KEY_OK 0x02u
+#define OURO_LV_LEADER_OK 0x04u
+#define OURO_LV_KES_PERIOD_OK 0x08u
+#define OURO_LV_COUNTER_OK 0x10u
+#define OURO_LV_OVERLAY 0x40u
+#define OURO_LV_BADARG 0x80u
+#define OURO_LV_ALL_OK 0x1fu
+#define OURO_LV_NO_POOL 0xffffffffu
+#define OURO_LV_ROWS_MAX ((size_t)1 << 24)
+/* A ledger-view schedule, shaped like ouro_epoch_nonces: entry j applies to
+ * first_slot[j] <= slot (the last such entry; found by the same binary
+ * search), and first_slot[j] is taken as the first slot of that epoch.  Entry
+ * j's pools are rows pool_begin[j] .. pool_begin[j + 1] of the flat arrays,
+ * sorted by the 28 id bytes as unsigned bytes, strictly ascending.
+ * OURO_EINVAL before anything runs: k outside 1 .. OURO_EPOCHS_MAX,
+ * first_slot[0] != 0 or not strictly increasing, pool_begin[0] != 0 or
+ * decreasing, more than OURO_LV_ROWS_MAX rows, rows out of order, d_den == 0,
+ * d_num > d_den, sigma_den == 0, sigma_num > sigma_den, a NULL array. */
+typedef struct ouro_ledger_views {
+  size_t k;
+  const uint64_t *first_slot; /* k                                              */
+  const uint64_t *d_num;      /* k    decentralisation parameter d = num / den  */
+  const uint64_t *d_den;      /* k                                              */
+  const uint32_t *pool_begin; /* k + 1                                          */
+  const uint8_t *pool_id;     /* rows x 28  hashKey of the pool's cold key      */
+  const uint8_t *vrf_hash;    /* rows x 32  hashVerKeyVRF of its VRF key        */
+  const uint64_t *sigma_num;  /* rows       relative stake = num / den          */
+  const uint64_t *sigma_den;  /* rows                                           */
+} ouro_ledger_views;
+/* slots_per_kes_period > 0 (OURO_EINVAL); act_log_* / f_is_one as
+ * ouro_leader_check_batch */
+typedef struct ouro_ledger_globals {
+  uint64_t slots_per_kes_period;
+  uint64_t max_kes_evo;
+  int64_t act_log_hi;
+  uint64_t act_log_lo;
+  int f_is_one;
+} ouro_ledger_globals;
+/* The OCERT counters a chain state holds (ChainDepState's csCounters): m pool
+ * ids, sorted like a view entry's rows, with counter[i] valid where
+ * present[i] != 0.  The table must contain every pool id of every view row
+ * (OURO_EINVAL otherwise): a pool in the distribution without a counter yet
+ * is a row with present = 0 -- currentIssueNo's "in the pool distribution"
+ * case, counter 0. */
+typedef struct ouro_ocert_counters {
+  size_t m;
+  const uint8_t *pool_id;  /* m x 28, strictly ascending */
+  const uint64_t *counter; /* m */
+  const uint8_t *present;  /* m */
+} ouro_ocert_counters;
+
+/* The OCERT rule's counter check (CounterTooSmallOCERT) over n headers in
+ * stream order, on the host, exact; the sibling of ouro_nonce_fold.  Header i
+ * is skipped when OURO_LV_POOL_KNOWN is clear in ledger[i] (a PBFT or unsliced
+ * header, an unknown pool) or OURO_LV_OVERLAY is set.  Otherwise, with m0 the
+ * pool's counter in the table (0 when not present): OURO_LV_COUNTER_OK is set
+ * in ledger[i] iff m0 <= ocert_counter[i]; then ocert_counter[i] is stored and
+ * the pool marked present AS GIVEN, whatever the verdict -- the way the
+ * envelope links to header i - 1 as given; the caller stops at the first
+ * invalid header.  pool_row[i]: the header's view row (ouro_tpraos_ledger_
+ * checks).  The updated table goes to counter_out / present_out (m each; may
+ * alias the inputs), so calls chain like tip_out.  The row-to-table index map
+ * is built once per call by merging the sorted lists. */
+int ouro_ocert_counter_fold(size_t n, const uint32_t *pool_row, const uint64_t *ocert_counter,
+                            const ouro_ledger_views *views, const ouro_ocert_counters *in,
+                            uint64_t *counter_out, uint8_t *present_out, uint8_t *ledger);
+
+/* The rules above for n sliced TPraos header rows (SoA host buffers: the
+ * columns of ouro_tpraos_batch, and the slots): ledger[i] = OURO_LV_* bits,
+ * pool_row[i] (may be NULL) = the absolute view row of the issuer, or
+ * OURO_LV_NO_POOL.  One lane per header on the GPU (k_ledger_checks); a
+ * device error recomputes on the host path; _host is the host path alone.
+ * counters (may be NULL, then ocert_counter, counter_out and present_out are
+ * unused and OURO_LV_COUNTER_OK stays clear): the fold above runs over the
+ * results.  Replaces, per header, the lookups and checkLeaderValue of
+ * ledger-specs' OVERLAY rule (vrfChecks) and the period and counter checks
+ * of its OCERT rule. */
+int ouro_tpraos_ledger_checks(size_t n, const uint8_t *issuer_vk, const uint8_t *vrf_vk,
+                              const uint64_t *slot, const uint8_t *leader_output,
+                              const uint64_t *ocert_kes_period, const uint64_t *ocert_counter,
+                              const ouro_ledger_views *views, const ouro_ledger_globals *globals,
+                              const ouro_ocert_counters *counters, uint64_t *counter_out,
+                              uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
+int ouro_tpraos_ledger_checks_host(size_t n, const uint8_t *issuer_vk, const uint8_t *vrf_vk,
+                                   const uint64_t *slot, const uint8_t *leader_output,
+                                   const uint64_t *ocert_kes_period,
+                                   const uint64_t *ocert_counter, const ouro_ledger_views *views,
+                                   const ouro_ledger_globals *globals,
+                                   const ouro_ocert_counters *counters, uint64_t *counter_out,
+                                   uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
+/* Device pointers on the caller's stream, not synchronised.  The views are
+ * checked, packed and uploaded once by ouro_ledger_views_upload (synchronous;
+ * on the calling thread's device) and released by ouro_ledger_views_free.
+ * OURO_LV_COUNTER_OK is not evaluated: pool_row (required) is what
+ * ouro_ocert_counter_fold needs once the results are on the host. */
+typedef struct ouro_ledger_views_dev ouro_ledger_views_dev;
+int ouro_ledger_views_upload(const ouro_ledger_views *views, ouro_ledger_views_dev **out);
+void ouro_ledger_views_free(ouro_ledger_views_dev *dv);
+int ouro_tpraos_ledger_checks_device(void *stream, size_t n, const uint8_t *issuer_vk,
+                                     const uint8_t *vrf_vk, const uint64_t *slot,
+                                     const uint8_t *leader_output,
+                                     const uint64_t *ocert_kes_period,
+                                     const ouro_ledger_views_dev *views,
+                                     const ouro_ledger_globals *globals, uint8_t *ledger,
+                                     uint32_t *pool_row);
+
+/* ouro_chain_validate_cbor with the ledger-view checks in the same call:
+ * every argument and result of that entry, unchanged, then the views, the
+ * globals (their slots_per_kes_period must equal the call's), the counters in
+ * and out (counters may be NULL: no fold) and ledger[n], pool_row[n] (may be
+ * NULL).  How it runs: the views are uploaded once per call and every chunk's
+ * stream waits on that upload; after a chunk's header kernel, on the chunk's
+ * stream, k_ledger_checks runs over the TPraos rows already in the slot's
+ * arena; the chunk copies back 13 more bytes per TPraos header (bits, row,
+ * counter) and a mixed chunk scatters them through the same index list as
+ * the verdicts; the fold runs in order as chunks drain.  A device error
+ * recomputes the batch on the host path, this stage included.  _host: the
+ * host path alone. */
+int ouro_chain_validate_ledger_cbor(
+    const uint8_t *raw, size_t raw_bytes, const uint64_t *off, const uint32_t *len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+    const uint8_t *eta_alpha, const uint8_t *leader_alpha, const ouro_envelope_cfg *cfg,
+    const ouro_chain_tip *tip_in, uint8_t *proto, uint8_t *status, uint8_t *verdict,
+    uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce, uint8_t *header_hash,
+    uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
+    const ouro_ledger_globals *globals, const ouro_ocert_counters *counters,
+    uint64_t *counter_out, uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
+int ouro_chain_validate_ledger_cbor_host(
+    const uint8_t *raw, size_t raw_bytes, const uint64_t *off, const uint32_t *len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+    const uint8_t *eta_alpha, const uint8_t *leader_alpha, const ouro_envelope_cfg *cfg,
+    const ouro_chain_tip *tip_in, uint8_t *proto, uint8_t *status, uint8_t *verdict,
+    uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce, uint8_t *header_hash,
+    uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
+    const ouro_ledger_globals *globals, const ouro_ocert_counters *counters,
+    uint64_t *counter_out, uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
 
 /* (How ouro_byron_verify_cbor runs, since round 6: on the raw-CBOR pipeline
  * of ouro_tpraos_verify_cbor -- chunks gathered into pinned NUMA-local

@@ -12,30 +12,37 @@ from .block import blake2b256_batch, parse_block, verify_block_integrity_cbor
 from .byron import (ByronDSIGN, dlg_cert_message, pack_byron_cbor, parse_byron_header,
                     verify_byron_cbor, verify_byron_headers, verify_delegation_certs)
 from .dsign import Ed25519DSIGN
-from .header import (chain_envelope_cbor, validate_chain_cbor, verify_chain_cbor,
-                     verify_headers_cbor, verify_integrity_cbor)
+from .header import (chain_envelope_cbor, validate_chain_cbor, validate_chain_ledger_cbor,
+                     verify_chain_cbor, verify_headers_cbor, verify_integrity_cbor)
+from .ledger import Counters, Globals, LedgerViews, counter_fold, ledger_checks
 from .kes import Sum6KES, kes_period
 from .tpraos import EpochNonces, HeaderBatch, first_invalid, verify_headers, verify_headers_multi
 from .vrf import PraosVRF
 
 __all__ = [
     "ByronDSIGN",
+    "Counters",
     "DeviceError",
     "Ed25519DSIGN",
     "EpochNonces",
+    "Globals",
     "HeaderBatch",
+    "LedgerViews",
     "NativeUnavailable",
     "PraosVRF",
     "Sum6KES",
     "blake2b256_batch",
     "chain_envelope_cbor",
+    "counter_fold",
     "first_invalid",
     "kes_period",
+    "ledger_checks",
     "dlg_cert_message",
     "pack_byron_cbor",
     "parse_block",
     "parse_byron_header",
     "validate_chain_cbor",
+    "validate_chain_ledger_cbor",
     "verify_block_integrity_cbor",
     "verify_byron_cbor",
     "verify_byron_headers",

@@ -49,6 +49,17 @@ PROTO_PBFT = 0     # ouro_chain_verify_cbor proto[i]: a Byron header
 PROTO_TPRAOS = 1   # a Shelley-family header (and anything unreadable)
 EPOCHS_MAX = 4096  # OURO_EPOCHS_MAX
 
+LV_POOL_KNOWN = 0x01     # ouro_tpraos_ledger_checks ledger[i]
+LV_VRF_KEY_OK = 0x02
+LV_LEADER_OK = 0x04
+LV_KES_PERIOD_OK = 0x08
+LV_COUNTER_OK = 0x10
+LV_OVERLAY = 0x40
+LV_BADARG = 0x80
+LV_ALL_OK = 0x1F
+LV_NO_POOL = 0xFFFFFFFF
+LV_ROWS_MAX = 1 << 24
+
 LEADER_NO = 0
 LEADER_YES = 1
 LEADER_BADARG = 0xFF
@@ -122,6 +133,29 @@ class EnvelopeCfg(ctypes.Structure):
                                                "max_major_pv")]
 
 
+class LedgerViewsC(ctypes.Structure):
+    """Mirror of ``ouro_ledger_views`` (include/ouro_verify.h)."""
+
+    _fields_ = [("k", ctypes.c_size_t)] + [
+        (f, ctypes.c_void_p) for f in ("first_slot", "d_num", "d_den", "pool_begin", "pool_id",
+                                       "vrf_hash", "sigma_num", "sigma_den")]
+
+
+class LedgerGlobalsC(ctypes.Structure):
+    """Mirror of ``ouro_ledger_globals`` (include/ouro_verify.h)."""
+
+    _fields_ = [("slots_per_kes_period", ctypes.c_uint64), ("max_kes_evo", ctypes.c_uint64),
+                ("act_log_hi", ctypes.c_int64), ("act_log_lo", ctypes.c_uint64),
+                ("f_is_one", ctypes.c_int)]
+
+
+class OcertCountersC(ctypes.Structure):
+    """Mirror of ``ouro_ocert_counters`` (include/ouro_verify.h)."""
+
+    _fields_ = [("m", ctypes.c_size_t), ("pool_id", ctypes.c_void_p),
+                ("counter", ctypes.c_void_p), ("present", ctypes.c_void_p)]
+
+
 # every symbol include/ouro_verify.h (the boundary) and include/ouro_verify_debug.h
 # (diagnostics) declare, with its ctypes signature
 _P = ctypes.c_void_p
@@ -181,6 +215,35 @@ SIGNATURES = {
                                            ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip),
                                            _P, _P, _P, _P, _P, _P, _P, _P,
                                            ctypes.POINTER(ChainTip)]),
+    "ouro_ocert_counter_fold": (_I, [_SZ, _P, _P, ctypes.POINTER(LedgerViewsC),
+                                     ctypes.POINTER(OcertCountersC), _P, _P, _P]),
+    "ouro_tpraos_ledger_checks": (_I, [_SZ, _P, _P, _P, _P, _P, _P, ctypes.POINTER(LedgerViewsC),
+                                       ctypes.POINTER(LedgerGlobalsC),
+                                       ctypes.POINTER(OcertCountersC), _P, _P, _P, _P]),
+    "ouro_tpraos_ledger_checks_host": (_I, [_SZ, _P, _P, _P, _P, _P, _P,
+                                            ctypes.POINTER(LedgerViewsC),
+                                            ctypes.POINTER(LedgerGlobalsC),
+                                            ctypes.POINTER(OcertCountersC), _P, _P, _P, _P]),
+    "ouro_ledger_views_upload": (_I, [ctypes.POINTER(LedgerViewsC), ctypes.POINTER(_P)]),
+    "ouro_ledger_views_free": (None, [_P]),
+    "ouro_tpraos_ledger_checks_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P,
+                                              ctypes.POINTER(LedgerGlobalsC), _P, _P]),
+    "ouro_chain_validate_ledger_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64,
+                                             ctypes.POINTER(EpochNonces), _P, _P,
+                                             ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip),
+                                             _P, _P, _P, _P, _P, _P, _P, _P,
+                                             ctypes.POINTER(ChainTip),
+                                             ctypes.POINTER(LedgerViewsC),
+                                             ctypes.POINTER(LedgerGlobalsC),
+                                             ctypes.POINTER(OcertCountersC), _P, _P, _P, _P]),
+    "ouro_chain_validate_ledger_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
+                                                  ctypes.c_int64, ctypes.POINTER(EpochNonces), _P,
+                                                  _P, ctypes.POINTER(EnvelopeCfg),
+                                                  ctypes.POINTER(ChainTip), _P, _P, _P, _P, _P, _P,
+                                                  _P, _P, ctypes.POINTER(ChainTip),
+                                                  ctypes.POINTER(LedgerViewsC),
+                                                  ctypes.POINTER(LedgerGlobalsC),
+                                                  ctypes.POINTER(OcertCountersC), _P, _P, _P, _P]),
     "ouro_chain_envelope_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ,
                                              ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip),
                                              _P, _SZ, _P, _P, _P, _P]),

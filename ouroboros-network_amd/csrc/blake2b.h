@@ -104,6 +104,58 @@ OURO_FI void blake2b256_short(uint32_t out[8], const uint32_t in[16], uint32_t l
 
 OURO_FI void blake2b256_64(uint32_t out[8], const uint32_t in[16]) { blake2b256_short(out, in, 64); }
 
+// out = Blake2b-224 (digest length 28: h0 = IV0 ^ 0x0101001c) of the first
+// `len` <= 64 bytes of in, bytes past len zero: one final compression with
+// counter t = len.  ledger-specs hashKey of a 32-byte cold key, the pool id
+// (ledger_view.h).  out[0..6] are the digest's 28 bytes as little-endian words.
+OURO_FI void blake2b224_short(uint32_t out[7], const uint32_t in[16], uint32_t len) {
+  const uint64_t IV[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
+                          0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
+                          0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+  uint64_t m[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) m[i] = (uint64_t)in[2 * i] | ((uint64_t)in[2 * i + 1] << 32);
+#pragma unroll
+  for (int i = 8; i < 16; i++) m[i] = 0;
+  const uint64_t h0 = IV[0] ^ 0x0101001cULL;  // digest length 28, no key, fanout 1, depth 1
+  uint64_t v[16];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    v[i] = i ? IV[i] : h0;
+    v[i + 8] = IV[i];
+  }
+  v[12] ^= len;   // t0 = bytes hashed
+  v[14] = ~v[14]; // final block
+#define OURO_B2G(a, b, c, d, x, y)                     \
+  v[a] = v[a] + v[b] + (x);                            \
+  v[d] = b2b_rotr(v[d] ^ v[a], 32);                    \
+  v[c] = v[c] + v[d];                                  \
+  v[b] = b2b_rotr(v[b] ^ v[c], 24);                    \
+  v[a] = v[a] + v[b] + (y);                            \
+  v[d] = b2b_rotr(v[d] ^ v[a], 16);                    \
+  v[c] = v[c] + v[d];                                  \
+  v[b] = b2b_rotr(v[b] ^ v[c], 63);
+#pragma unroll
+  for (int r = 0; r < 12; r++) {
+    const uint8_t* s = kB2bSigma[r];
+    OURO_B2G(0, 4, 8, 12, m[s[0]], m[s[1]])
+    OURO_B2G(1, 5, 9, 13, m[s[2]], m[s[3]])
+    OURO_B2G(2, 6, 10, 14, m[s[4]], m[s[5]])
+    OURO_B2G(3, 7, 11, 15, m[s[6]], m[s[7]])
+    OURO_B2G(0, 5, 10, 15, m[s[8]], m[s[9]])
+    OURO_B2G(1, 6, 11, 12, m[s[10]], m[s[11]])
+    OURO_B2G(2, 7, 8, 13, m[s[12]], m[s[13]])
+    OURO_B2G(3, 4, 9, 14, m[s[14]], m[s[15]])
+  }
+#undef OURO_B2G
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const uint64_t x = (i ? IV[i] : h0) ^ v[i] ^ v[i + 8];
+    out[2 * i] = (uint32_t)x;
+    if (i < 3) out[2 * i + 1] = (uint32_t)(x >> 32);
+  }
+}
+
 // ---- mkSeed / mkNonceFromNumber ----------------------
 // seedEta = mkNonceFromNumber 0, seedL = mkNonceFromNumber 1, i.e.
 // Blake2b-256(BE64(0 / 1)) as little-endian words.  Pinned by

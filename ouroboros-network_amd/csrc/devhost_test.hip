@@ -12,6 +12,7 @@
 
 #include "blake2b_stream.h"
 #include "leader.h"
+#include "ledger_view.h"
 #include "tpraos.h"
 
 using namespace ouro;
@@ -297,6 +298,22 @@ void dh_elligator2_ref(uint8_t* out, const uint8_t* r32) {
 int dh_leader_check(const uint8_t* beta64, uint64_t num, uint64_t den, uint64_t act_log_lo,
                     int64_t act_log_hi) {
   return leader_check_lane(beta64, num, den, act_log_lo, act_log_hi);
+}
+// ledger_view.h: the OURO_LV_* bits (COUNTER_OK excepted) of one header row and
+// its view row; blake2b.h: Blake2b-224 of 32 bytes
+int dh_ledger_check(const ouro_ledger_views* v, const ouro_ledger_globals* g,
+                    const uint8_t* issuer_vk, const uint8_t* vrf_vk, uint64_t slot,
+                    const uint8_t* leader_output, uint64_t c0, uint32_t* pool_row) {
+  return lv::ledger_check_lane(*v, *g, issuer_vk, vrf_vk, slot, leader_output, c0, pool_row);
+}
+int dh_is_overlay_slot(uint64_t s, uint64_t num, uint64_t den) {
+  return lv::is_overlay_slot(s, num, den) ? 1 : 0;
+}
+void dh_blake2b224_32(const uint8_t* in32, uint8_t* out28) {
+  uint32_t in[16], o[7];
+  for (int w = 0; w < 16; w++) in[w] = w < 8 ? ld_le32(in32 + 4 * w) : 0u;
+  blake2b224_short(o, in, 32);
+  for (int k = 0; k < 28; k++) out28[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
 }
 // lattice.h: (|c0|, c1, sign of c0) for h (32 bytes, < 2^253); returns the bit size
 int dh_half_scalars(const uint8_t* h32, uint8_t* c0, uint8_t* c1, int* c0_neg) {

@@ -47,6 +47,13 @@ int launch_leader(hipStream_t st, size_t n, const uint8_t* beta, const uint64_t*
                   const uint64_t* den, int64_t lhi, uint64_t llo, int f_is_one,
                   uint8_t* verdict);
 
+// the ledger-view checks (ledger_view.h k_ledger_checks) over n sliced header
+// rows; v: a schedule whose pointers are device pointers, 8-byte aligned
+int launch_ledger(hipStream_t st, size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk,
+                  const uint64_t* slot, const uint8_t* leader_output,
+                  const uint64_t* ocert_kes_period, const ouro_ledger_views& v,
+                  const ouro_ledger_globals& g, uint8_t* ledger, uint32_t* pool_row);
+
 // latency mode: eight cores per header (x4 lanes in quad mode), then the
 // finish; n and the option bits read from d_n[0..1].
 // Lanes used <= the kBlock-rounded count lowlat_scratch_words provides for.

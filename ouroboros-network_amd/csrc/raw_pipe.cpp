@@ -61,6 +61,10 @@ using namespace ouro_rt;
 // RawCall::env set: behind each chunk's work, on the same stream, the envelope
 // kernels (launches.h launch_envelope) over the chunk in the caller's order;
 // raw_drain links each chunk's first header to the chunk before it.
+// A ledger call (ouro_chain_validate_ledger_cbor) is a validating call with
+// RawCall::ledger set: the views uploaded once, k_ledger_checks behind each
+// chunk's header kernel over the rows in the slot's arena (launches.h
+// launch_ledger), the OCERT counter fold in stream order as chunks drain.
 namespace {
 constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kRawChunkBytes = (size_t)96 << 20;
@@ -139,6 +143,20 @@ RawEnvOut raw_env_out(size_t m) {
   e.status = e.ends + 2 * sizeof(env::Rec);
   e.total = e.status + a16(m);
   return e;
+}
+
+// a ledger call's block of a chunk's mt TPraos rows: bits | view rows on the
+// device and in pinned memory, where the rows' counter column follows
+struct RawLvOut {
+  size_t bits, rows, ctr, total;
+};
+RawLvOut raw_lv_out(size_t mt) {
+  RawLvOut l;
+  l.bits = 0;
+  l.rows = a16(mt);
+  l.ctr = l.rows + a16(4 * mt);
+  l.total = l.ctr + 8 * mt;
+  return l;
 }
 
 // Every span inside raw (as ouro_tpraos_pack_cbor demands), and the chunks.
@@ -314,7 +332,8 @@ int raw_launch_tpraos(RawSlot& s, const RawCall& c, const uint8_t* draw, size_t 
   const size_t blocks = std::min<size_t>((mt + kBlock - 1) / kBlock, 4096);
   uint64_t* dslot = reinterpret_cast<uint64_t*>(dout + O.slot);
   const bool seeds = c.kind != kRawKes && !dea;
-  const cbor::Out o = cbor::arena_out(arena, mt, seeds ? dslot : nullptr, nullptr);
+  // (a ledger call needs the slots whatever seeds the VRF inputs)
+  const cbor::Out o = cbor::arena_out(arena, mt, seeds || c.ledger ? dslot : nullptr, nullptr);
   launch_tpraos_pack(s.st, (unsigned)blocks, draw, raw_bytes, doff, dlen, mt, c.spkp, o,
                      dout + O.status);
   int rc;
@@ -332,7 +351,44 @@ int raw_launch_tpraos(RawSlot& s, const RawCall& c, const uint8_t* draw, size_t 
     b.epoch_nonce = deta0;
   }
   if (c.nonce) b.eta_nonce = dout + O.nonce;
-  return launch_hdr(s.st, b, dout + O.verdict, dout + O.be, dout + O.bl, dea ? nullptr : dtab);
+  if ((rc = launch_hdr(s.st, b, dout + O.verdict, dout + O.be, dout + O.bl, dea ? nullptr : dtab)) ||
+      !c.ledger)
+    return rc;
+  // the ledger-view checks behind the header kernel, on the same stream, over
+  // the rows already in the arena; the views were uploaded once for the call
+  const RawLvOut LO = raw_lv_out(mt);
+  if ((rc = ensure(s.d_lv, LO.ctr)) || (rc = pinned_at_least(&s.h_lv, &s.h_lv_cap, LO.total)))
+    return rc;
+  uint8_t* dlv = static_cast<uint8_t*>(s.d_lv.p);
+  OURO_HIP(hipStreamWaitEvent(s.st, c.ledger->uploaded, 0));
+  if ((rc = launch_ledger(s.st, mt, b.issuer_vk, b.vrf_vk, dslot, b.leader_output,
+                          b.ocert_kes_period, c.ledger->dviews, c.ledger->g, dlv + LO.bits,
+                          reinterpret_cast<uint32_t*>(dlv + LO.rows))))
+    return rc;
+  OURO_HIP(hipMemcpyAsync(s.h_lv, dlv, LO.ctr, hipMemcpyDeviceToHost, s.st));
+  OURO_HIP(hipMemcpyAsync(s.h_lv + LO.ctr, b.ocert_counter, 8 * mt, hipMemcpyDeviceToHost, s.st));
+  return OURO_OK;
+}
+
+// a drained chunk's ledger results into the caller's order, then the counter
+// fold over them in that order (idx: a mixed chunk's TPraos rows' indices,
+// ascending, or null: row j is header j)
+void raw_drain_ledger(const RawSlot& s, const RawCall& c, size_t mt, const uint32_t* idx,
+                      const uint8_t* status) {
+  RawLedger& L = *c.ledger;
+  memset(L.ledger + s.lo, 0, s.m);
+  for (size_t i = 0; i < s.m; i++) L.pool_row[s.lo + i] = OURO_LV_NO_POOL;
+  const RawLvOut LO = raw_lv_out(mt);
+  const uint8_t* bits = s.h_lv + LO.bits;
+  const uint32_t* rows = reinterpret_cast<const uint32_t*>(s.h_lv + LO.rows);
+  const uint64_t* ctr = reinterpret_cast<const uint64_t*>(s.h_lv + LO.ctr);
+  for (size_t j = 0; j < mt; j++) {
+    if (status[j] != OURO_PACK_OK) continue;  // (its zeroed row says nothing)
+    const size_t i = s.lo + (idx ? idx[j] : j);
+    L.ledger[i] = bits[j];
+    L.pool_row[i] = rows[j];
+    if (L.fold) lv_fold_run(L.fold, 1, &rows[j], &ctr[j], &L.ledger[i]);
+  }
 }
 
 // the slot's stream: upload, device slicer(s), kernel(s), results back
@@ -443,6 +499,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
     const RawOut O = raw_out(mt);
     const RawOutB OB = raw_out_b(mb);
     const uint8_t* h = s.h_out;
+    if (c.ledger) raw_drain_ledger(s, c, mt, s.idx.data(), h + O.status);
     for (size_t j = 0; j < mt; j++) {
       const size_t i = s.lo + s.idx[j];
       const uint8_t st = h[O.status + j];
@@ -473,6 +530,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
     // (ouroboros-consensus/src/Ouroboros/Consensus/Protocol/PBFT.hs:327-328)
     for (size_t i = 0; i < s.m; i++)
       c.verdict[s.lo + i] = st[i] == OURO_PACK_EBB ? 1 : (st[i] == OURO_PACK_OK && v[i] ? 1 : 0);
+    if (c.ledger) raw_drain_ledger(s, c, 0, nullptr, st);
     if (hdr) {  // the combined entry: a PBFT header has no VRF outputs
       if (c.be) memset(c.be + 64 * s.lo, 0, 64 * s.m);
       if (c.bl) memset(c.bl + 64 * s.lo, 0, 64 * s.m);
@@ -484,6 +542,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
   // masked so that no bit at all is set for it)
   for (size_t i = 0; i < s.m; i++) c.verdict[s.lo + i] = st[i] == OURO_PACK_OK ? v[i] : 0;
   if (c.kind == kRawBlock && c.body_hash) memcpy(c.body_hash + 32 * s.lo, s.h_out + O.be, 32 * s.m);
+  if (c.ledger) raw_drain_ledger(s, c, s.m, nullptr, st);
   if (hdr) {
     if (c.be) memcpy(c.be + 64 * s.lo, s.h_out + O.be, 64 * s.m);
     if (c.bl) memcpy(c.bl + 64 * s.lo, s.h_out + O.bl, 64 * s.m);
@@ -516,6 +575,16 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
   }
   const int width = (int)knob_size(ouro_knobs::get().cbor_copy_threads, 8, 1, 64);
   if (c.env) c.env->prev = c.env->tip;
+  if (c.ledger) {
+    // the views once per call, on the first slot's stream; every chunk's
+    // stream waits on the upload before its ledger kernel
+    if (!p.views_up) OURO_HIP(hipEventCreateWithFlags(&p.views_up, hipEventDisableTiming));
+    if ((rc = lv_upload(p.s[0].st, *c.ledger->views, &p.d_views, &c.ledger->packed,
+                        &c.ledger->dviews)))
+      return rc;
+    OURO_HIP(hipEventRecord(p.views_up, p.s[0].st));
+    c.ledger->uploaded = p.views_up;
+  }
   size_t ci = 0;
   for (; ci < chunks.size() && !rc; ci++) {
     RawSlot& s = p.s[ci % S];
@@ -570,6 +639,51 @@ int raw_host_byron(const RawCall& c) {
 }
 
 int raw_host(const RawCall& c);
+
+// a ledger call on the host path: the TPraos headers sliced again on the host
+// in chunks, ledger_check_lane over their rows, the fold in stream order
+// (c.proto and c.status are the chain kind's, already written)
+int raw_host_ledger(const RawCall& c) {
+  RawLedger& L = *c.ledger;
+  const size_t C = 1 << 16;
+  std::vector<uint32_t> ix, rows;
+  std::vector<uint64_t> off, slots;
+  std::vector<uint32_t> len;
+  std::vector<uint8_t> st, bits, arena;
+  for (size_t lo = 0; lo < c.n; lo += C) {
+    const size_t m = std::min(C, c.n - lo);
+    memset(L.ledger + lo, 0, m);
+    ix.clear();
+    for (size_t i = lo; i < lo + m; i++) {
+      L.pool_row[i] = OURO_LV_NO_POOL;
+      if (c.proto[i] == OURO_PROTO_TPRAOS) ix.push_back((uint32_t)(i - lo));
+    }
+    const size_t q = ix.size();
+    if (!q) continue;
+    off.resize(q), len.resize(q), slots.resize(q), st.resize(q), bits.resize(q), rows.resize(q);
+    for (size_t j = 0; j < q; j++) {
+      off[j] = c.off[lo + ix[j]];
+      len[j] = c.len[lo + ix[j]];
+    }
+    arena.resize(ouro_tpraos_pack_bytes(q));
+    ouro_tpraos_batch b{};
+    int rc = ouro_tpraos_pack_cbor(c.raw, c.raw_bytes, off.data(), len.data(), q, c.spkp,
+                                   arena.data(), arena.size(), &b, slots.data(), nullptr, st.data(),
+                                   0);
+    if (rc) return fail(rc, "ouro_tpraos_pack_cbor: bad arguments");
+    if ((rc = lv_host_rows(q, b.issuer_vk, b.vrf_vk, slots.data(), b.leader_output,
+                           b.ocert_kes_period, *L.views, L.g, bits.data(), rows.data())))
+      return rc;
+    for (size_t j = 0; j < q; j++) {
+      if (st[j] != OURO_PACK_OK) continue;
+      const size_t i = lo + ix[j];
+      L.ledger[i] = bits[j];
+      L.pool_row[i] = rows[j];
+      if (L.fold) lv_fold_run(L.fold, 1, &rows[j], &b.ocert_counter[j], &L.ledger[i]);
+    }
+  }
+  return OURO_OK;
+}
 
 // The combined entry on the host path: per chunk of 64 K headers the same
 // partition as a mixed device chunk -- each class's offset / length (and
@@ -643,6 +757,8 @@ int raw_host(const RawCall& c) {
   if (c.kind == kRawChain) {
     try {  // (its lists are vectors; no exception crosses the C ABI)
       if (int rc = raw_host_chain(c)) return rc;
+      if (c.ledger)
+        if (int rc = raw_host_ledger(c)) return rc;
       if (!c.env) return OURO_OK;
       // a validating call: the envelope with the host build of the same routines
       if (int rc = env_host_run(c.raw, c.off, c.len, c.n, c.env->cfg, c.env->tip, nullptr,
@@ -892,6 +1008,120 @@ int ouro_chain_validate_cbor_host(const uint8_t* raw, size_t raw_bytes, const ui
   if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
                           epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
                           beta_leader, eta_nonce))
+    return rc;
+  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
+                             envelope, tip_out))
+    return rc;
+  return raw_verify_host(a.c);
+}
+
+// validateHeader with the ledger-view checks of SL.updateChainDepState
+// (Shelley/Protocol.hs:433-442; ledger-specs OVERLAY and OCERT) in the same
+// call: the validating call above with RawCall ledger set.
+namespace {
+struct LedgerArgs {
+  RawLedger l{};
+  LvFold fold;
+  std::vector<uint32_t> map, rows;
+  // the table as the call found it: a device error recomputes from it
+  std::vector<uint64_t> counter0;
+  std::vector<uint8_t> present0;
+  ouro_ocert_counters t0{};
+};
+int ledger_call(ChainArgs* a, LedgerArgs* g, size_t n, uint64_t spkp,
+                const ouro_ledger_views* views, const ouro_ledger_globals* globals,
+                const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
+                uint8_t* ledger, uint32_t* pool_row) {
+  int rc;
+  if ((rc = lv_views_check(views)) || (rc = lv_globals_check(globals))) return rc;
+  if (globals->slots_per_kes_period != spkp)
+    return fail(OURO_EINVAL, "globals: slots_per_kes_period differs from the call's");
+  if (n && !ledger) return fail(OURO_EINVAL, "null ledger");
+  if ((rc = lv_counters_check(counters, counter_out, present_out))) return rc;
+  if (counters && (rc = lv_fold_map(*views, *counters, &g->map))) return rc;
+  try {  // (no exception crosses the C ABI)
+    if (!pool_row) {
+      g->rows.resize(n);
+      pool_row = g->rows.data();
+    }
+    if (counters) {
+      g->counter0.assign(counters->counter, counters->counter + counters->m);
+      g->present0.assign(counters->present, counters->present + counters->m);
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(OURO_EDEVICE, "ledger call: out of host memory");
+  }
+  g->l.views = views;
+  g->l.g = *globals;
+  g->l.ledger = ledger;
+  g->l.pool_row = pool_row;
+  if (counters) {
+    g->t0 = ouro_ocert_counters{counters->m, counters->pool_id, g->counter0.data(),
+                                g->present0.data()};
+    lv_fold_begin(&g->fold, g->t0, &g->map, counter_out, present_out);
+    g->l.fold = &g->fold;
+  }
+  a->c.ledger = &g->l;
+  return OURO_OK;
+}
+// the device pipeline, or after a device error the host path from the
+// table as the call found it (the pipeline's fold may have moved it)
+int ledger_verify(ChainArgs* a, LedgerArgs* g) {
+  if (a->c.n == 0) return OURO_OK;
+  if (int rc0 = raw_check(a->c)) return rc0;
+  std::vector<RawChunk> chunks;
+  const size_t per = knob_size(ouro_knobs::get().cbor_chunk, 65536, 256, (size_t)1 << 24);
+  if (int rc = raw_chunks(a->c, per, &chunks)) return rc;
+  return or_host(raw_run(a->c, chunks), [&] {
+    if (g->l.fold) lv_fold_begin(&g->fold, g->t0, &g->map, g->fold.counter, g->fold.present);
+    return raw_host(a->c);
+  });
+}
+}  // namespace
+
+int ouro_chain_validate_ledger_cbor(
+    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
+    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
+    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
+    const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
+    uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
+  ChainArgs a;
+  RawEnv e{};
+  LedgerArgs g;
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, globals, counters, counter_out,
+                           present_out, ledger, pool_row))
+    return rc;
+  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
+                             envelope, tip_out))
+    return rc;
+  return ledger_verify(&a, &g);
+}
+
+int ouro_chain_validate_ledger_cbor_host(
+    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
+    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
+    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
+    const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
+    uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
+  ChainArgs a;
+  RawEnv e{};
+  LedgerArgs g;
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, globals, counters, counter_out,
+                           present_out, ledger, pool_row))
     return rc;
   if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
                              envelope, tip_out))

@@ -119,6 +119,11 @@ struct RawSlot {
   Buf d_env;
   uint8_t* h_env = nullptr;
   size_t h_env_cap = 0;
+  // the ledger-view checks of a call with RawCall ledger: bits | rows on the
+  // device; bits | rows | the counter column in pinned memory
+  Buf d_lv;
+  uint8_t* h_lv = nullptr;
+  size_t h_lv_cap = 0;
   size_t lo = 0, m = 0;
   bool busy = false;
   // the combined entry (kRawChain): the chunk's era make-up and, for a mixed
@@ -132,6 +137,8 @@ enum RawMode { kModeTpraos = 0, kModeByron = 1, kModeMixed = 2 };
 struct RawPipe {
   bool ready = false;
   RawSlot s[kRawMaxSlots];
+  Buf d_views;  // a call's packed ledger views (RawLedger), uploaded once per call
+  hipEvent_t views_up = nullptr;
 };
 
 // Everything a calling thread needs on one device: its stream, the scratch
@@ -279,6 +286,42 @@ struct RawEnv {
   uint8_t *hash, *envelope;  // OUT: n x 32, n
   ouro_chain_tip* tip_out;   // OUT, or null
 };
+// ---- the ledger-view checks (ledger_api.cpp; ledger_view.h) ----
+// the OCERT counter fold's state: the view-row -> table-index map and the
+// table being updated (the caller's counter_out / present_out)
+struct LvFold {
+  const std::vector<uint32_t>* map = nullptr;
+  uint64_t* counter = nullptr;
+  uint8_t* present = nullptr;
+};
+int lv_views_check(const ouro_ledger_views* v);
+int lv_globals_check(const ouro_ledger_globals* g);
+int lv_counters_check(const ouro_ocert_counters* t, const uint64_t* counter_out,
+                      const uint8_t* present_out);
+int lv_host_rows(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk, const uint64_t* slot,
+                 const uint8_t* leader_output, const uint64_t* c0, const ouro_ledger_views& v,
+                 const ouro_ledger_globals& g, uint8_t* ledger, uint32_t* pool_row);
+int lv_upload(hipStream_t st, const ouro_ledger_views& v, Buf* buf, std::vector<uint8_t>* host,
+              ouro_ledger_views* d);
+int lv_fold_map(const ouro_ledger_views& v, const ouro_ocert_counters& t,
+                std::vector<uint32_t>* map);
+void lv_fold_begin(LvFold* f, const ouro_ocert_counters& t, const std::vector<uint32_t>* map,
+                   uint64_t* counter_out, uint8_t* present_out);
+void lv_fold_run(LvFold* f, size_t n, const uint32_t* pool_row, const uint64_t* counter,
+                 uint8_t* ledger);
+// What ouro_chain_validate_ledger_cbor adds to a validating call: the views
+// (uploaded once per call: dviews, `uploaded` for the chunks' streams to wait
+// on), the fold (or null) and the outputs.
+struct RawLedger {
+  const ouro_ledger_views* views;
+  ouro_ledger_globals g;
+  LvFold* fold;        // null: no counters given
+  uint8_t* ledger;     // OUT: n
+  uint32_t* pool_row;  // OUT: n
+  ouro_ledger_views dviews{};
+  std::vector<uint8_t> packed;
+  hipEvent_t uploaded = nullptr;
+};
 struct RawCall {
   RawKind kind;
   const uint8_t* raw;
@@ -299,6 +342,7 @@ struct RawCall {
   size_t epochs_bytes = 0;
   uint8_t* body_hash = nullptr;  // block kind: OUT, the computed bbHash (n x 32), or null
   RawEnv* env = nullptr;         // chain kind: also the header envelope (validate), or null
+  RawLedger* ledger = nullptr;   // chain kind: also the ledger-view checks, or null
 };
 int raw_verify(const RawCall& c);
 // block_api.cpp: the block kind's device sequence on one stream (a: the

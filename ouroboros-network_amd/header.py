@@ -698,3 +698,63 @@ def validate_chain_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: 
         crypto += (en[:n],)
     valid = np.where(proto[:n] == PROTO_PBFT, verdict[:n] == 1, (verdict[:n] & 0x0F) == 0x0F)
     return crypto, hh[:n], bits[:n], _py_tip(t_out), E.first_invalid(bits[:n], valid)
+
+
+def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: int,
+                               views, globals_, *, counters=None, cfg=None, tip=None,
+                               epochs: Optional[EpochNonces] = None,
+                               eta_alpha: Optional[np.ndarray] = None,
+                               leader_alpha: Optional[np.ndarray] = None, nonce: bool = False,
+                               host: bool = False):
+    """validate_chain_cbor with the ledger-view checks in the same call
+    (include/ouro_verify.h ouro_chain_validate_ledger_cbor): `views` (a
+    ledger.LedgerViews), `globals_` (a ledger.Globals) and optionally the OCERT
+    `counters` (a ledger.Counters) for the counter fold.  Returns
+    validate_chain_cbor's tuple and then (ledger, pool_row, counters_after):
+    the LV_* bits (0 for a PBFT or unsliced header), each issuer's view row,
+    and the table after the fold (None without counters)."""
+    import ctypes
+
+    from . import _native
+    from . import envelope as E
+    buf, off, ln = raw_triplet(raw_headers)
+    n = int(off.size)
+    if ln.size != n:
+        raise ValueError("off / len: one entry per header")
+    m = max(n, 1)
+    proto, status, verdict = (np.zeros(m, np.uint8) for _ in range(3))
+    be = np.zeros((m, 64), np.uint8)
+    bl = np.zeros((m, 64), np.uint8)
+    en = np.zeros((m, 32), np.uint8) if nonce else None
+    hh = np.zeros((m, 32), np.uint8)
+    bits = np.zeros(m, np.uint8)
+    ledger = np.zeros(m, np.uint8)
+    rows = np.zeros(m, np.uint32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    ea = None if eta_alpha is None else np.ascontiguousarray(eta_alpha, np.uint8).reshape(n, 32)
+    la = None if leader_alpha is None else \
+        np.ascontiguousarray(leader_alpha, np.uint8).reshape(n, 32)
+    e = None if epochs is None else ctypes.byref(epochs.c_struct())
+    c_cfg, t_in, t_out = _c_cfg(cfg or E.Cfg()), _c_tip(tip), _native.ChainTip()
+    cv, cg = views.c_struct(), globals_.c_struct()
+    cc = co = po = None
+    if counters is not None:
+        cc = counters.c_struct()
+        co, po = np.zeros_like(counters.counter), np.zeros_like(counters.present)
+    lib = _native.load()
+    name = "ouro_chain_validate_ledger_cbor" + ("_host" if host else "")
+    rc = getattr(lib, name)(ptr(buf), buf.size, ptr(off), ptr(ln), n, slots_per_kes_period,
+                            protocol_magic, e, ptr(ea), ptr(la), ctypes.byref(c_cfg),
+                            ctypes.byref(t_in), ptr(proto), ptr(status), ptr(verdict), ptr(be),
+                            ptr(bl), ptr(en), ptr(hh), ptr(bits), ctypes.byref(t_out),
+                            ctypes.byref(cv), ctypes.byref(cg),
+                            None if cc is None else ctypes.byref(cc), ptr(co), ptr(po),
+                            ptr(ledger), ptr(rows))
+    _native.check(rc, name)
+    crypto = (proto[:n], status[:n], verdict[:n], be[:n], bl[:n])
+    if nonce:
+        crypto += (en[:n],)
+    valid = np.where(proto[:n] == PROTO_PBFT, verdict[:n] == 1, (verdict[:n] & 0x0F) == 0x0F)
+    after = None if counters is None else counters.after(co, po)
+    return (crypto, hh[:n], bits[:n], _py_tip(t_out), E.first_invalid(bits[:n], valid),
+            ledger[:n], rows[:n], after)
