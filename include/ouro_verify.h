@@ -806,9 +806,13 @@ int ouro_chain_validate_cbor_host(const uint8_t *raw, size_t raw_bytes, const ui
  *                   (CounterTooSmallOCERT): ouro_ocert_counter_fold
  *   OVERLAY         the slot is an overlay slot (ledger-specs isOverlaySlot:
  *                   ceil(s d) < ceil((s + 1) d), s = slot - the entry's
- *                   first_slot, exact integers; d_num == 0: never).  Then only
- *                   KES_PERIOD_OK is evaluated: the genesis-delegate branch
- *                   (pbftVrfChecks) stays with the caller.
+ *                   first_slot, exact integers; d_num == 0: never).  Without
+ *                   a genesis-delegation schedule (ouro_genesis_delegs below)
+ *                   only KES_PERIOD_OK is evaluated then and the fold skips
+ *                   the row; with one, the genesis-delegate branch
+ *                   (pbftVrfChecks) is evaluated as the table below says.
+ *   OVERLAY_ACTIVE  (with a schedule only) the overlay slot is an active one
+ *                                                   (else NotActiveSlotOVERLAY)
  *   BADARG          the leader check's arguments are outside its domain
  *                   (OURO_LEADER_BADARG); LEADER_OK is then clear. */
 #define OURO_LV_POOL_KNOWN 0x01u
@@ -816,11 +820,13 @@ int ouro_chain_validate_cbor_host(const uint8_t *raw, size_t raw_bytes, const ui
 #define OURO_LV_LEADER_OK 0x04u
 #define OURO_LV_KES_PERIOD_OK 0x08u
 #define OURO_LV_COUNTER_OK 0x10u
+#define OURO_LV_OVERLAY_ACTIVE 0x20u
 #define OURO_LV_OVERLAY 0x40u
 #define OURO_LV_BADARG 0x80u
 #define OURO_LV_ALL_OK 0x1fu
 #define OURO_LV_NO_POOL 0xffffffffu
 #define OURO_LV_ROWS_MAX ((size_t)1 << 24)
+#define OURO_LV_GEN_ROWS_MAX ((size_t)1 << 16)
 /* A ledger-view schedule, shaped like ouro_epoch_nonces: entry j applies to
  * first_slot[j] <= slot (the last such entry; found by the same binary
  * search), and first_slot[j] is taken as the first slot of that epoch.  Entry
@@ -863,6 +869,43 @@ typedef struct ouro_ocert_counters {
   const uint8_t *present;  /* m */
 } ouro_ocert_counters;
 
+/* The genesis delegations of a ledger-view schedule, for the overlay slots
+ * (ledger-specs OVERLAY rule's other branch: lookupInOverlaySchedule, then
+ * pbftVrfChecks; the reference walks it first, Shelley/Protocol.hs:366-399).
+ * Entry j belongs to view entry j; its rows are its genesis keys, sorted by
+ * the 28 id bytes as Map.keysSet gives them (Protocol.hs:406), each with the
+ * GenDelegPair it maps to.  For a TPraos row of entry j on an overlay slot,
+ * with s = slot - first_slot[j] and d = d_num[j] / d_den[j], exact integers:
+ *   position = ceil(s d);  the slot is ACTIVE iff position mod asc_inv == 0;
+ *   then the scheduled genesis key is row (position div asc_inv) mod ngen of
+ *   the entry (Set.elemAt: a direct index), and
+ *     POOL_KNOWN     active and Blake2b-224(issuer_vk) == delegate_id[row]
+ *                                              (else WrongGenesisColdKeyOVERLAY)
+ *     VRF_KEY_OK     POOL_KNOWN and Blake2b-256(vrf_vk) == delegate_vrf[row]
+ *                                              (else WrongGenesisVRFKeyOVERLAY)
+ *     LEADER_OK      = POOL_KNOWN: no threshold on an overlay slot; BADARG never
+ *     KES_PERIOD_OK  as on any slot
+ *     COUNTER_OK     the fold, keyed by delegate_id[row] in the same counters
+ *                    table (currentIssueNo: 0 for a delegate without a counter)
+ *   and pool_row[i] is the absolute genesis row when POOL_KNOWN, else
+ *   OURO_LV_NO_POOL: OVERLAY tells which table the row indexes.  A valid header
+ *   has (bits & OURO_LV_ALL_OK) == OURO_LV_ALL_OK on either kind of slot.
+ * asc_inv = floor(1 / f) >= 1 is an input of its own: it cannot be derived
+ * exactly from act_log_*.
+ * OURO_EINVAL before anything runs: k != views->k, gen_begin[0] != 0 or
+ * decreasing, more than OURO_LV_GEN_ROWS_MAX rows, genesis_id not strictly
+ * ascending inside an entry, asc_inv == 0, an entry with d_num > 0 and no rows
+ * (the reference divides by zero there), a NULL array; with counters, a
+ * delegate_id the counters table has no row for. */
+typedef struct ouro_genesis_delegs {
+  size_t k;
+  const uint32_t *gen_begin;   /* k + 1                                         */
+  const uint8_t *genesis_id;   /* rows x 28  hashKey of the genesis key         */
+  const uint8_t *delegate_id;  /* rows x 28  genDelegKeyHash                    */
+  const uint8_t *delegate_vrf; /* rows x 32  genDelegVrfHash                    */
+  uint64_t asc_inv;            /* floor(1 / f)                                  */
+} ouro_genesis_delegs;
+
 /* The OCERT rule's counter check (CounterTooSmallOCERT) over n headers in
  * stream order, on the host, exact; the sibling of ouro_nonce_fold.  Header i
  * is skipped when OURO_LV_POOL_KNOWN is clear in ledger[i] (a PBFT or unsliced
@@ -878,6 +921,15 @@ typedef struct ouro_ocert_counters {
 int ouro_ocert_counter_fold(size_t n, const uint32_t *pool_row, const uint64_t *ocert_counter,
                             const ouro_ledger_views *views, const ouro_ocert_counters *in,
                             uint64_t *counter_out, uint8_t *present_out, uint8_t *ledger);
+/* The same fold with a genesis-delegation schedule (NULL: exactly the fold
+ * above): a header with OURO_LV_OVERLAY and OURO_LV_POOL_KNOWN is folded too,
+ * its pool_row[i] a genesis row and its key delegate_id[row] -- one table, so
+ * a pool row and a delegate row of the same id share a counter. */
+int ouro_ocert_counter_fold_overlay(size_t n, const uint32_t *pool_row,
+                                    const uint64_t *ocert_counter, const ouro_ledger_views *views,
+                                    const ouro_genesis_delegs *genesis,
+                                    const ouro_ocert_counters *in, uint64_t *counter_out,
+                                    uint8_t *present_out, uint8_t *ledger);
 
 /* The rules above for n sliced TPraos header rows (SoA host buffers: the
  * columns of ouro_tpraos_batch, and the slots): ledger[i] = OURO_LV_* bits,
@@ -902,6 +954,28 @@ int ouro_tpraos_ledger_checks_host(size_t n, const uint8_t *issuer_vk, const uin
                                    const ouro_ledger_globals *globals,
                                    const ouro_ocert_counters *counters, uint64_t *counter_out,
                                    uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
+/* The same with a genesis-delegation schedule (NULL: exactly the entries
+ * above, row for row): overlay rows are evaluated by the delegate branch in
+ * the same kernel launch and folded against the delegates' ids. */
+int ouro_tpraos_ledger_checks_overlay(size_t n, const uint8_t *issuer_vk, const uint8_t *vrf_vk,
+                                      const uint64_t *slot, const uint8_t *leader_output,
+                                      const uint64_t *ocert_kes_period,
+                                      const uint64_t *ocert_counter, const ouro_ledger_views *views,
+                                      const ouro_genesis_delegs *genesis,
+                                      const ouro_ledger_globals *globals,
+                                      const ouro_ocert_counters *counters, uint64_t *counter_out,
+                                      uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
+int ouro_tpraos_ledger_checks_overlay_host(size_t n, const uint8_t *issuer_vk,
+                                           const uint8_t *vrf_vk, const uint64_t *slot,
+                                           const uint8_t *leader_output,
+                                           const uint64_t *ocert_kes_period,
+                                           const uint64_t *ocert_counter,
+                                           const ouro_ledger_views *views,
+                                           const ouro_genesis_delegs *genesis,
+                                           const ouro_ledger_globals *globals,
+                                           const ouro_ocert_counters *counters,
+                                           uint64_t *counter_out, uint8_t *present_out,
+                                           uint8_t *ledger, uint32_t *pool_row);
 /* Device pointers on the caller's stream, not synchronised.  The views are
  * checked, packed and uploaded once by ouro_ledger_views_upload (synchronous;
  * on the calling thread's device) and released by ouro_ledger_views_free.
@@ -909,6 +983,12 @@ int ouro_tpraos_ledger_checks_host(size_t n, const uint8_t *issuer_vk, const uin
  * ouro_ocert_counter_fold needs once the results are on the host. */
 typedef struct ouro_ledger_views_dev ouro_ledger_views_dev;
 int ouro_ledger_views_upload(const ouro_ledger_views *views, ouro_ledger_views_dev **out);
+/* The views and a genesis-delegation schedule (NULL: the upload above) checked
+ * and packed into ONE device block.  ouro_tpraos_ledger_checks_device on such a
+ * handle evaluates overlay rows by the delegate branch. */
+int ouro_ledger_views_upload_overlay(const ouro_ledger_views *views,
+                                     const ouro_genesis_delegs *genesis,
+                                     ouro_ledger_views_dev **out);
 void ouro_ledger_views_free(ouro_ledger_views_dev *dv);
 int ouro_tpraos_ledger_checks_device(void *stream, size_t n, const uint8_t *issuer_vk,
                                      const uint8_t *vrf_vk, const uint64_t *slot,
@@ -948,6 +1028,30 @@ int ouro_chain_validate_ledger_cbor_host(
     uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
     const ouro_ledger_globals *globals, const ouro_ocert_counters *counters,
     uint64_t *counter_out, uint8_t *present_out, uint8_t *ledger, uint32_t *pool_row);
+/* The same with a genesis-delegation schedule after the views (NULL: exactly
+ * the entries above).  The schedule is checked, packed and uploaded once per
+ * call in the views' block, behind the same event; nothing more is copied per
+ * chunk and the results stay 13 bytes per TPraos header. */
+int ouro_chain_validate_ledger_overlay_cbor(
+    const uint8_t *raw, size_t raw_bytes, const uint64_t *off, const uint32_t *len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+    const uint8_t *eta_alpha, const uint8_t *leader_alpha, const ouro_envelope_cfg *cfg,
+    const ouro_chain_tip *tip_in, uint8_t *proto, uint8_t *status, uint8_t *verdict,
+    uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce, uint8_t *header_hash,
+    uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
+    const ouro_genesis_delegs *genesis, const ouro_ledger_globals *globals,
+    const ouro_ocert_counters *counters, uint64_t *counter_out, uint8_t *present_out,
+    uint8_t *ledger, uint32_t *pool_row);
+int ouro_chain_validate_ledger_overlay_cbor_host(
+    const uint8_t *raw, size_t raw_bytes, const uint64_t *off, const uint32_t *len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+    const uint8_t *eta_alpha, const uint8_t *leader_alpha, const ouro_envelope_cfg *cfg,
+    const ouro_chain_tip *tip_in, uint8_t *proto, uint8_t *status, uint8_t *verdict,
+    uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce, uint8_t *header_hash,
+    uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
+    const ouro_genesis_delegs *genesis, const ouro_ledger_globals *globals,
+    const ouro_ocert_counters *counters, uint64_t *counter_out, uint8_t *present_out,
+    uint8_t *ledger, uint32_t *pool_row);
 
 /* (How ouro_byron_verify_cbor runs, since round 6: on the raw-CBOR pipeline
  * of ouro_tpraos_verify_cbor -- chunks gathered into pinned NUMA-local

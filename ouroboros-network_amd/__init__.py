@@ -14,7 +14,8 @@ from .byron import (ByronDSIGN, dlg_cert_message, pack_byron_cbor, parse_byron_h
 from .dsign import Ed25519DSIGN
 from .header import (chain_envelope_cbor, validate_chain_cbor, validate_chain_ledger_cbor,
                      verify_chain_cbor, verify_headers_cbor, verify_integrity_cbor)
-from .ledger import Counters, Globals, LedgerViews, counter_fold, ledger_checks
+from .ledger import (Counters, GenesisDelegs, Globals, LedgerViews, counter_fold,
+                     ledger_checks)
 from .kes import Sum6KES, kes_period
 from .tpraos import EpochNonces, HeaderBatch, first_invalid, verify_headers, verify_headers_multi
 from .vrf import PraosVRF
@@ -26,6 +27,7 @@ __all__ = [
     "Ed25519DSIGN",
     "EpochNonces",
     "Globals",
+    "GenesisDelegs",
     "HeaderBatch",
     "LedgerViews",
     "NativeUnavailable",

@@ -54,11 +54,13 @@ LV_VRF_KEY_OK = 0x02
 LV_LEADER_OK = 0x04
 LV_KES_PERIOD_OK = 0x08
 LV_COUNTER_OK = 0x10
+LV_OVERLAY_ACTIVE = 0x20  # with a genesis-delegation schedule: an active overlay slot
 LV_OVERLAY = 0x40
 LV_BADARG = 0x80
 LV_ALL_OK = 0x1F
 LV_NO_POOL = 0xFFFFFFFF
 LV_ROWS_MAX = 1 << 24
+LV_GEN_ROWS_MAX = 1 << 16
 
 LEADER_NO = 0
 LEADER_YES = 1
@@ -156,6 +158,14 @@ class OcertCountersC(ctypes.Structure):
                 ("counter", ctypes.c_void_p), ("present", ctypes.c_void_p)]
 
 
+class GenesisDelegsC(ctypes.Structure):
+    """Mirror of ``ouro_genesis_delegs`` (include/ouro_verify.h)."""
+
+    _fields_ = [("k", ctypes.c_size_t)] + [
+        (f, ctypes.c_void_p) for f in ("gen_begin", "genesis_id", "delegate_id",
+                                       "delegate_vrf")] + [("asc_inv", ctypes.c_uint64)]
+
+
 # every symbol include/ouro_verify.h (the boundary) and include/ouro_verify_debug.h
 # (diagnostics) declare, with its ctypes signature
 _P = ctypes.c_void_p
@@ -225,6 +235,43 @@ SIGNATURES = {
                                             ctypes.POINTER(LedgerGlobalsC),
                                             ctypes.POINTER(OcertCountersC), _P, _P, _P, _P]),
     "ouro_ledger_views_upload": (_I, [ctypes.POINTER(LedgerViewsC), ctypes.POINTER(_P)]),
+    "ouro_ocert_counter_fold_overlay": (_I, [_SZ, _P, _P, ctypes.POINTER(LedgerViewsC),
+                                             ctypes.POINTER(GenesisDelegsC),
+                                             ctypes.POINTER(OcertCountersC), _P, _P, _P]),
+    "ouro_tpraos_ledger_checks_overlay": (_I, [_SZ, _P, _P, _P, _P, _P, _P,
+                                               ctypes.POINTER(LedgerViewsC),
+                                               ctypes.POINTER(GenesisDelegsC),
+                                               ctypes.POINTER(LedgerGlobalsC),
+                                               ctypes.POINTER(OcertCountersC), _P, _P, _P, _P]),
+    "ouro_tpraos_ledger_checks_overlay_host": (_I, [_SZ, _P, _P, _P, _P, _P, _P,
+                                                    ctypes.POINTER(LedgerViewsC),
+                                                    ctypes.POINTER(GenesisDelegsC),
+                                                    ctypes.POINTER(LedgerGlobalsC),
+                                                    ctypes.POINTER(OcertCountersC), _P, _P, _P,
+                                                    _P]),
+    "ouro_ledger_views_upload_overlay": (_I, [ctypes.POINTER(LedgerViewsC),
+                                              ctypes.POINTER(GenesisDelegsC), ctypes.POINTER(_P)]),
+    "ouro_chain_validate_ledger_overlay_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
+                                                     ctypes.c_int64, ctypes.POINTER(EpochNonces),
+                                                     _P, _P, ctypes.POINTER(EnvelopeCfg),
+                                                     ctypes.POINTER(ChainTip), _P, _P, _P, _P, _P,
+                                                     _P, _P, _P, ctypes.POINTER(ChainTip),
+                                                     ctypes.POINTER(LedgerViewsC),
+                                                     ctypes.POINTER(GenesisDelegsC),
+                                                     ctypes.POINTER(LedgerGlobalsC),
+                                                     ctypes.POINTER(OcertCountersC), _P, _P, _P,
+                                                     _P]),
+    "ouro_chain_validate_ledger_overlay_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
+                                                          ctypes.c_int64,
+                                                          ctypes.POINTER(EpochNonces), _P, _P,
+                                                          ctypes.POINTER(EnvelopeCfg),
+                                                          ctypes.POINTER(ChainTip), _P, _P, _P, _P,
+                                                          _P, _P, _P, _P, ctypes.POINTER(ChainTip),
+                                                          ctypes.POINTER(LedgerViewsC),
+                                                          ctypes.POINTER(GenesisDelegsC),
+                                                          ctypes.POINTER(LedgerGlobalsC),
+                                                          ctypes.POINTER(OcertCountersC), _P, _P,
+                                                          _P, _P]),
     "ouro_ledger_views_free": (None, [_P]),
     "ouro_tpraos_ledger_checks_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P,
                                               ctypes.POINTER(LedgerGlobalsC), _P, _P]),

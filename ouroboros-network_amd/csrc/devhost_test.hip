@@ -306,6 +306,24 @@ int dh_ledger_check(const ouro_ledger_views* v, const ouro_ledger_globals* g,
                     const uint8_t* leader_output, uint64_t c0, uint32_t* pool_row) {
   return lv::ledger_check_lane(*v, *g, issuer_vk, vrf_vk, slot, leader_output, c0, pool_row);
 }
+// the same with a genesis-delegation schedule: overlay rows take the delegate
+// branch
+int dh_ledger_check_overlay(const ouro_ledger_views* v, const ouro_ledger_globals* g,
+                            const ouro_genesis_delegs* gd, const uint8_t* issuer_vk,
+                            const uint8_t* vrf_vk, uint64_t slot, const uint8_t* leader_output,
+                            uint64_t c0, uint32_t* pool_row) {
+  return lv::ledger_check_lane<true>(*v, *g, *gd, issuer_vk, vrf_vk, slot, leader_output, c0,
+                                     pool_row);
+}
+// classifyOverlaySlot: -1 not an overlay slot, -2 inactive, else the index of
+// the scheduled genesis key
+int64_t dh_classify_overlay_slot(uint64_t s, uint64_t num, uint64_t den, uint64_t asc_inv,
+                                 uint32_t ngen) {
+  uint64_t position;
+  if (!lv::overlay_position(s, num, den, &position)) return -1;
+  const uint32_t ix = lv::overlay_index(position, asc_inv, ngen);
+  return ix == OURO_LV_NO_POOL ? -2 : (int64_t)ix;
+}
 int dh_is_overlay_slot(uint64_t s, uint64_t num, uint64_t den) {
   return lv::is_overlay_slot(s, num, den) ? 1 : 0;
 }

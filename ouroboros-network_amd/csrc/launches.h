@@ -53,6 +53,13 @@ int launch_ledger(hipStream_t st, size_t n, const uint8_t* issuer_vk, const uint
                   const uint64_t* slot, const uint8_t* leader_output,
                   const uint64_t* ocert_kes_period, const ouro_ledger_views& v,
                   const ouro_ledger_globals& g, uint8_t* ledger, uint32_t* pool_row);
+// the same with a genesis-delegation schedule of device pointers
+// (k_ledger_checks_overlay)
+int launch_ledger_overlay(hipStream_t st, size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk,
+                          const uint64_t* slot, const uint8_t* leader_output,
+                          const uint64_t* ocert_kes_period, const ouro_ledger_views& v,
+                          const ouro_ledger_globals& g, const ouro_genesis_delegs& gd,
+                          uint8_t* ledger, uint32_t* pool_row);
 
 // latency mode: eight cores per header (x4 lanes in quad mode), then the
 // finish; n and the option bits read from d_n[0..1].

@@ -25,6 +25,8 @@ struct ouro_ledger_views_dev {
   int dev;
   void* block;
   ouro_ledger_views d;  // device pointers into block
+  bool has_genesis;     // uploaded with a genesis-delegation schedule:
+  ouro_genesis_delegs g;  // device pointers into the same block
 };
 
 namespace {
@@ -33,14 +35,20 @@ constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 int cmp28(const uint8_t* a, const uint8_t* b) { return memcmp(a, b, 28); }
 
 // the rows of a (checked) schedule packed as one block; *d: the same schedule
-// with its pointers at `base` + the block's offsets
-size_t lv_pack(const ouro_ledger_views& v, std::vector<uint8_t>* blk, ouro_ledger_views* d,
-               const uint8_t* base) {
+// with its pointers at `base` + the block's offsets.  gd (or null): a checked
+// genesis-delegation schedule packed behind the views in the same block -- what
+// the kernel reads of it: gen_begin, delegate_id, delegate_vrf; *dgd likewise
+// (its genesis_id stays null: the order matters to the argument check alone)
+size_t lv_pack(const ouro_ledger_views& v, const ouro_genesis_delegs* gd, std::vector<uint8_t>* blk,
+               ouro_ledger_views* d, ouro_genesis_delegs* dgd, const uint8_t* base) {
   const size_t k = v.k, rows = v.pool_begin[k];
   const size_t o_fs = 0, o_dn = o_fs + a16(8 * k), o_dd = o_dn + a16(8 * k), o_pb = o_dd + a16(8 * k);
   const size_t o_sn = o_pb + a16(4 * (k + 1)), o_sd = o_sn + a16(8 * rows);
   const size_t o_vh = o_sd + a16(8 * rows), o_id = o_vh + a16(32 * rows);
-  const size_t total = o_id + a16(28 * rows) + 16;
+  const size_t grows = gd ? gd->gen_begin[k] : 0;
+  const size_t o_gb = o_id + a16(28 * rows) + 16, o_gi = o_gb + (gd ? a16(4 * (k + 1)) : 0);
+  const size_t o_gv = o_gi + a16(28 * grows);
+  const size_t total = gd ? o_gv + a16(32 * grows) + 16 : o_gb;
   if (blk) {
     blk->assign(total, 0);
     uint8_t* p = blk->data();
@@ -54,6 +62,11 @@ size_t lv_pack(const ouro_ledger_views& v, std::vector<uint8_t>* blk, ouro_ledge
       memcpy(p + o_vh, v.vrf_hash, 32 * rows);
       memcpy(p + o_id, v.pool_id, 28 * rows);
     }
+    if (gd) memcpy(p + o_gb, gd->gen_begin, 4 * (k + 1));
+    if (grows) {
+      memcpy(p + o_gi, gd->delegate_id, 28 * grows);
+      memcpy(p + o_gv, gd->delegate_vrf, 32 * grows);
+    }
   }
   if (d) {
     d->k = k;
@@ -65,6 +78,14 @@ size_t lv_pack(const ouro_ledger_views& v, std::vector<uint8_t>* blk, ouro_ledge
     d->sigma_den = reinterpret_cast<const uint64_t*>(base + o_sd);
     d->vrf_hash = base + o_vh;
     d->pool_id = base + o_id;
+  }
+  if (gd && dgd) {
+    dgd->k = k;
+    dgd->gen_begin = reinterpret_cast<const uint32_t*>(base + o_gb);
+    dgd->genesis_id = nullptr;
+    dgd->delegate_id = base + o_gi;
+    dgd->delegate_vrf = base + o_gv;
+    dgd->asc_inv = gd->asc_inv;
   }
   return total;
 }
@@ -85,12 +106,12 @@ int rows_check(const RowArgs& r, const uint8_t* ledger, bool need_counter) {
 }
 
 int lv_dev(const RowArgs& r, const ouro_ledger_views& v, const ouro_ledger_globals& g,
-           uint8_t* ledger, uint32_t* pool_row) {
+           const ouro_genesis_delegs* gd, uint8_t* ledger, uint32_t* pool_row) {
   hipStream_t st;
   int rc = thread_stream(&st);
   if (rc) return rc;
   std::vector<uint8_t> blk;
-  lv_pack(v, &blk, nullptr, nullptr);
+  lv_pack(v, gd, &blk, nullptr, nullptr, nullptr);
   Stager sg{st};
   const uint8_t* dblk = sg.up(blk.data(), blk.size());
   auto dis = sg.up(r.issuer_vk, 32 * r.n);
@@ -102,8 +123,10 @@ int lv_dev(const RowArgs& r, const ouro_ledger_views& v, const ouro_ledger_globa
   auto dr = sg.out<uint32_t>(r.n);
   if (sg.rc) return sg.rc;
   ouro_ledger_views d;
-  lv_pack(v, nullptr, &d, dblk);
-  if ((rc = launch_ledger(st, r.n, dis, dvk, dsl, dlo, dc0, d, g, dl, dr))) return rc;
+  ouro_genesis_delegs dgd{};
+  lv_pack(v, gd, nullptr, &d, &dgd, dblk);
+  if ((rc = lv_launch(st, r.n, dis, dvk, dsl, dlo, dc0, d, g, gd ? &dgd : nullptr, dl, dr)))
+    return rc;
   std::vector<uint8_t> tl(r.n);
   std::vector<uint32_t> tr(r.n);
   if ((rc = download(st, tl.data(), dl, r.n))) return rc;
@@ -114,15 +137,17 @@ int lv_dev(const RowArgs& r, const ouro_ledger_views& v, const ouro_ledger_globa
   return OURO_OK;
 }
 
-int rows_call(const RowArgs& r, const ouro_ledger_views* v, const ouro_ledger_globals* g,
-              const ouro_ocert_counters* t, uint64_t* counter_out, uint8_t* present_out,
-              uint8_t* ledger, uint32_t* pool_row, bool host) {
+int rows_call(const RowArgs& r, const ouro_ledger_views* v, const ouro_genesis_delegs* gd,
+              const ouro_ledger_globals* g, const ouro_ocert_counters* t, uint64_t* counter_out,
+              uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row, bool host) {
   int rc;
   if ((rc = lv_views_check(v)) || (rc = lv_globals_check(g)) ||
+      (gd && (rc = lv_genesis_check(gd, *v))) ||
       (rc = lv_counters_check(t, counter_out, present_out)))
     return rc;
-  std::vector<uint32_t> map, rows;
+  std::vector<uint32_t> map, gmap, rows;
   if (t && (rc = lv_fold_map(*v, *t, &map))) return rc;
+  if (t && gd && (rc = lv_fold_gmap(*gd, *t, &gmap))) return rc;
   if (r.n) {
     if ((rc = rows_check(r, ledger, t != nullptr))) return rc;
     if (!pool_row) {
@@ -130,15 +155,15 @@ int rows_call(const RowArgs& r, const ouro_ledger_views* v, const ouro_ledger_gl
       pool_row = rows.data();
     }
     auto on_host = [&] {
-      return lv_host_rows(r.n, r.issuer_vk, r.vrf_vk, r.slot, r.leader_output, r.c0, *v, *g, ledger,
-                          pool_row);
+      return lv_host_rows(r.n, r.issuer_vk, r.vrf_vk, r.slot, r.leader_output, r.c0, *v, *g, gd,
+                          ledger, pool_row);
     };
-    rc = host ? on_host() : or_host(lv_dev(r, *v, *g, ledger, pool_row), on_host);
+    rc = host ? on_host() : or_host(lv_dev(r, *v, *g, gd, ledger, pool_row), on_host);
     if (rc) return rc;
   }
   if (t) {
     LvFold f;
-    lv_fold_begin(&f, *t, &map, counter_out, present_out);
+    lv_fold_begin(&f, *t, &map, gd ? &gmap : nullptr, counter_out, present_out);
     lv_fold_run(&f, r.n, pool_row, r.counter, ledger);
   }
   return OURO_OK;
@@ -187,6 +212,33 @@ int lv_globals_check(const ouro_ledger_globals* g) {
   return OURO_OK;
 }
 
+// everything that is OURO_EINVAL in a genesis-delegation schedule beside its
+// (checked) views, the counters table's rows excepted (lv_fold_gmap)
+int lv_genesis_check(const ouro_genesis_delegs* gd, const ouro_ledger_views& v) {
+  if (!gd) return fail(OURO_EINVAL, "null genesis delegations");
+  if (gd->k != v.k) return fail(OURO_EINVAL, "genesis delegations: k differs from the views'");
+  if (gd->asc_inv == 0) return fail(OURO_EINVAL, "genesis delegations: asc_inv must be >= 1");
+  if (!gd->gen_begin) return fail(OURO_EINVAL, "genesis delegations: null array");
+  if (gd->gen_begin[0] != 0) return fail(OURO_EINVAL, "genesis delegations: gen_begin[0] must be 0");
+  for (size_t j = 0; j < gd->k; j++) {
+    const std::string at = "genesis delegations: entry " + std::to_string(j);
+    if (gd->gen_begin[j + 1] < gd->gen_begin[j]) return fail(OURO_EINVAL, at + ": gen_begin decreasing");
+    if (gd->gen_begin[j + 1] > OURO_LV_GEN_ROWS_MAX)
+      return fail(OURO_EINVAL, at + ": more than OURO_LV_GEN_ROWS_MAX rows");
+    if (v.d_num[j] > 0 && gd->gen_begin[j + 1] == gd->gen_begin[j])
+      return fail(OURO_EINVAL, at + ": d > 0 and no genesis keys");
+  }
+  const size_t rows = gd->gen_begin[gd->k];
+  if (rows && (!gd->genesis_id || !gd->delegate_id || !gd->delegate_vrf))
+    return fail(OURO_EINVAL, "genesis delegations: null row array");
+  for (size_t j = 0; j < gd->k; j++)
+    for (size_t r = gd->gen_begin[j] + (size_t)1; r < gd->gen_begin[j + 1]; r++)
+      if (cmp28(gd->genesis_id + 28 * (r - 1), gd->genesis_id + 28 * r) >= 0)
+        return fail(OURO_EINVAL, "genesis delegations: row " + std::to_string(r) +
+                                     ": genesis ids not strictly ascending");
+  return OURO_OK;
+}
+
 // a counters table and its outputs (t may be null: no fold)
 int lv_counters_check(const ouro_ocert_counters* t, const uint64_t* counter_out,
                       const uint8_t* present_out) {
@@ -203,12 +255,16 @@ int lv_counters_check(const ouro_ocert_counters* t, const uint64_t* counter_out,
 // the host path: ledger_check_lane over the rows on the worker pool
 int lv_host_rows(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk, const uint64_t* slot,
                  const uint8_t* leader_output, const uint64_t* c0, const ouro_ledger_views& v,
-                 const ouro_ledger_globals& g, uint8_t* ledger, uint32_t* pool_row) {
+                 const ouro_ledger_globals& g, const ouro_genesis_delegs* gd, uint8_t* ledger,
+                 uint32_t* pool_row) {
   const size_t per = 256, tasks = (n + per - 1) / per;
   auto work = [&](size_t t) {
     for (size_t i = t * per; i < std::min(n, (t + 1) * per); i++)
-      ledger[i] = lv::ledger_check_lane(v, g, issuer_vk + 32 * i, vrf_vk + 32 * i, slot[i],
-                                        leader_output + 64 * i, c0[i], &pool_row[i]);
+      ledger[i] = gd ? lv::ledger_check_lane<true>(v, g, *gd, issuer_vk + 32 * i, vrf_vk + 32 * i,
+                                                   slot[i], leader_output + 64 * i, c0[i],
+                                                   &pool_row[i])
+                     : lv::ledger_check_lane(v, g, issuer_vk + 32 * i, vrf_vk + 32 * i, slot[i],
+                                             leader_output + 64 * i, c0[i], &pool_row[i]);
   };
   if (tasks <= 1) {
     if (tasks) work(0);
@@ -218,15 +274,27 @@ int lv_host_rows(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk, cons
   return OURO_OK;
 }
 
-// a checked schedule packed and uploaded on `st` (not synchronised; *host
-// must stay alive until the copy has completed)
-int lv_upload(hipStream_t st, const ouro_ledger_views& v, Buf* buf, std::vector<uint8_t>* host,
-              ouro_ledger_views* d) {
-  lv_pack(v, host, nullptr, nullptr);
+// a checked schedule (and genesis-delegation schedule, or null) packed and
+// uploaded as one block on `st` (not synchronised; *host must stay alive until
+// the copy has completed)
+int lv_upload(hipStream_t st, const ouro_ledger_views& v, const ouro_genesis_delegs* gd, Buf* buf,
+              std::vector<uint8_t>* host, ouro_ledger_views* d, ouro_genesis_delegs* dgd) {
+  lv_pack(v, gd, host, nullptr, nullptr, nullptr);
   if (int rc = ensure(*buf, host->size())) return rc;
   OURO_HIP(hipMemcpyAsync(buf->p, host->data(), host->size(), hipMemcpyHostToDevice, st));
-  lv_pack(v, nullptr, d, static_cast<const uint8_t*>(buf->p));
+  lv_pack(v, gd, nullptr, d, dgd, static_cast<const uint8_t*>(buf->p));
   return OURO_OK;
+}
+
+// k_ledger_checks, or with a schedule k_ledger_checks_overlay
+int lv_launch(hipStream_t st, size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk,
+              const uint64_t* slot, const uint8_t* leader_output, const uint64_t* ocert_kes_period,
+              const ouro_ledger_views& v, const ouro_ledger_globals& g,
+              const ouro_genesis_delegs* gd, uint8_t* ledger, uint32_t* pool_row) {
+  return gd ? launch_ledger_overlay(st, n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period,
+                                    v, g, *gd, ledger, pool_row)
+            : launch_ledger(st, n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, v, g,
+                            ledger, pool_row);
 }
 
 // map[r] = the table index of view row r: each entry's sorted rows merged
@@ -247,9 +315,36 @@ int lv_fold_map(const ouro_ledger_views& v, const ouro_ocert_counters& t,
   return OURO_OK;
 }
 
+// gmap[r] = the table index of genesis row r's delegate_id.  The delegates of
+// an entry are in their genesis keys' order, so each entry's rows are sorted by
+// delegate id first and then merged with the sorted table like the pools'.
+int lv_fold_gmap(const ouro_genesis_delegs& gd, const ouro_ocert_counters& t,
+                 std::vector<uint32_t>* gmap) {
+  gmap->assign(gd.gen_begin[gd.k], 0);
+  std::vector<uint32_t> order;
+  for (size_t j = 0; j < gd.k; j++) {
+    order.clear();
+    for (uint32_t r = gd.gen_begin[j]; r < gd.gen_begin[j + 1]; r++) order.push_back(r);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+      return cmp28(gd.delegate_id + 28 * (size_t)a, gd.delegate_id + 28 * (size_t)b) < 0;
+    });
+    size_t q = 0;
+    for (const uint32_t r : order) {
+      const uint8_t* id = gd.delegate_id + 28 * (size_t)r;
+      while (q < t.m && cmp28(t.pool_id + 28 * q, id) < 0) q++;
+      if (q == t.m || cmp28(t.pool_id + 28 * q, id) != 0)
+        return fail(OURO_EINVAL,
+                    "counters: no row for the delegate id of genesis row " + std::to_string(r));
+      (*gmap)[r] = (uint32_t)q;
+    }
+  }
+  return OURO_OK;
+}
+
 void lv_fold_begin(LvFold* f, const ouro_ocert_counters& t, const std::vector<uint32_t>* map,
-                   uint64_t* counter_out, uint8_t* present_out) {
+                   const std::vector<uint32_t>* gmap, uint64_t* counter_out, uint8_t* present_out) {
   f->map = map;
+  f->gmap = gmap;
   f->counter = counter_out;
   f->present = present_out;
   if (t.m && counter_out != t.counter) memmove(counter_out, t.counter, 8 * t.m);
@@ -259,9 +354,11 @@ void lv_fold_begin(LvFold* f, const ouro_ocert_counters& t, const std::vector<ui
 void lv_fold_run(LvFold* f, size_t n, const uint32_t* pool_row, const uint64_t* counter,
                  uint8_t* ledger) {
   for (size_t i = 0; i < n; i++) {
-    if (!(ledger[i] & OURO_LV_POOL_KNOWN) || (ledger[i] & OURO_LV_OVERLAY)) continue;
-    if (pool_row[i] >= f->map->size()) continue;  // (never with POOL_KNOWN from the rule)
-    const uint32_t q = (*f->map)[pool_row[i]];
+    if (!(ledger[i] & OURO_LV_POOL_KNOWN)) continue;
+    // an overlay row's row is a genesis row: its key is the delegate's id
+    const std::vector<uint32_t>* m = (ledger[i] & OURO_LV_OVERLAY) ? f->gmap : f->map;
+    if (!m || pool_row[i] >= m->size()) continue;  // (never with POOL_KNOWN from the rule)
+    const uint32_t q = (*m)[pool_row[i]];
     const uint64_t m0 = f->present[q] ? f->counter[q] : 0;  // currentIssueNo
     if (m0 <= counter[i]) ledger[i] |= OURO_LV_COUNTER_OK;
     else ledger[i] &= (uint8_t)~OURO_LV_COUNTER_OK;
@@ -276,19 +373,31 @@ extern "C" {
 
 // ledger-specs OCERT rule, CounterTooSmallOCERT: the counter never goes back
 // per pool, in stream order
+int ouro_ocert_counter_fold_overlay(size_t n, const uint32_t* pool_row,
+                                    const uint64_t* ocert_counter, const ouro_ledger_views* views,
+                                    const ouro_genesis_delegs* genesis,
+                                    const ouro_ocert_counters* in, uint64_t* counter_out,
+                                    uint8_t* present_out, uint8_t* ledger) {
+  int rc;
+  if (!in) return fail(OURO_EINVAL, "null counters");
+  if ((rc = lv_views_check(views)) || (genesis && (rc = lv_genesis_check(genesis, *views))) ||
+      (rc = lv_counters_check(in, counter_out, present_out)))
+    return rc;
+  if (n && (!pool_row || !ocert_counter || !ledger)) return fail(OURO_EINVAL, "null argument");
+  std::vector<uint32_t> map, gmap;
+  if ((rc = lv_fold_map(*views, *in, &map))) return rc;
+  if (genesis && (rc = lv_fold_gmap(*genesis, *in, &gmap))) return rc;
+  LvFold f;
+  lv_fold_begin(&f, *in, &map, genesis ? &gmap : nullptr, counter_out, present_out);
+  lv_fold_run(&f, n, pool_row, ocert_counter, ledger);
+  return OURO_OK;
+}
+
 int ouro_ocert_counter_fold(size_t n, const uint32_t* pool_row, const uint64_t* ocert_counter,
                             const ouro_ledger_views* views, const ouro_ocert_counters* in,
                             uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger) {
-  int rc;
-  if (!in) return fail(OURO_EINVAL, "null counters");
-  if ((rc = lv_views_check(views)) || (rc = lv_counters_check(in, counter_out, present_out))) return rc;
-  if (n && (!pool_row || !ocert_counter || !ledger)) return fail(OURO_EINVAL, "null argument");
-  std::vector<uint32_t> map;
-  if ((rc = lv_fold_map(*views, *in, &map))) return rc;
-  LvFold f;
-  lv_fold_begin(&f, *in, &map, counter_out, present_out);
-  lv_fold_run(&f, n, pool_row, ocert_counter, ledger);
-  return OURO_OK;
+  return ouro_ocert_counter_fold_overlay(n, pool_row, ocert_counter, views, nullptr, in, counter_out,
+                                         present_out, ledger);
 }
 
 // ledger-specs OVERLAY (vrfChecks: VRFKeyUnknown, VRFKeyWrongVRFKey,
@@ -301,7 +410,8 @@ int ouro_tpraos_ledger_checks(size_t n, const uint8_t* issuer_vk, const uint8_t*
                               const ouro_ocert_counters* counters, uint64_t* counter_out,
                               uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
   const RowArgs r{n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, ocert_counter};
-  return rows_call(r, views, globals, counters, counter_out, present_out, ledger, pool_row, false);
+  return rows_call(r, views, nullptr, globals, counters, counter_out, present_out, ledger, pool_row,
+                   false);
 }
 
 int ouro_tpraos_ledger_checks_host(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk,
@@ -312,19 +422,57 @@ int ouro_tpraos_ledger_checks_host(size_t n, const uint8_t* issuer_vk, const uin
                                    const ouro_ocert_counters* counters, uint64_t* counter_out,
                                    uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
   const RowArgs r{n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, ocert_counter};
-  return rows_call(r, views, globals, counters, counter_out, present_out, ledger, pool_row, true);
+  return rows_call(r, views, nullptr, globals, counters, counter_out, present_out, ledger, pool_row,
+                   true);
 }
 
-int ouro_ledger_views_upload(const ouro_ledger_views* views, ouro_ledger_views_dev** out) {
+// the same with the OVERLAY rule's genesis-delegate branch (lookupInOverlay
+// Schedule; pbftVrfChecks: NotActiveSlotOVERLAY, WrongGenesisColdKeyOVERLAY,
+// WrongGenesisVRFKeyOVERLAY) on overlay slots
+int ouro_tpraos_ledger_checks_overlay(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk,
+                                      const uint64_t* slot, const uint8_t* leader_output,
+                                      const uint64_t* ocert_kes_period,
+                                      const uint64_t* ocert_counter, const ouro_ledger_views* views,
+                                      const ouro_genesis_delegs* genesis,
+                                      const ouro_ledger_globals* globals,
+                                      const ouro_ocert_counters* counters, uint64_t* counter_out,
+                                      uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
+  const RowArgs r{n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, ocert_counter};
+  return rows_call(r, views, genesis, globals, counters, counter_out, present_out, ledger, pool_row,
+                   false);
+}
+
+int ouro_tpraos_ledger_checks_overlay_host(size_t n, const uint8_t* issuer_vk,
+                                           const uint8_t* vrf_vk, const uint64_t* slot,
+                                           const uint8_t* leader_output,
+                                           const uint64_t* ocert_kes_period,
+                                           const uint64_t* ocert_counter,
+                                           const ouro_ledger_views* views,
+                                           const ouro_genesis_delegs* genesis,
+                                           const ouro_ledger_globals* globals,
+                                           const ouro_ocert_counters* counters,
+                                           uint64_t* counter_out, uint8_t* present_out,
+                                           uint8_t* ledger, uint32_t* pool_row) {
+  const RowArgs r{n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, ocert_counter};
+  return rows_call(r, views, genesis, globals, counters, counter_out, present_out, ledger, pool_row,
+                   true);
+}
+
+int ouro_ledger_views_upload_overlay(const ouro_ledger_views* views,
+                                     const ouro_genesis_delegs* genesis,
+                                     ouro_ledger_views_dev** out) {
   if (!out) return fail(OURO_EINVAL, "null out");
   *out = nullptr;
   if (int rc = lv_views_check(views)) return rc;
+  if (genesis)
+    if (int rc = lv_genesis_check(genesis, *views)) return rc;
   DeviceState* ds;
   int dev, rc = device_state(&ds);
   if (rc || (rc = current_device(&dev))) return rc;
   std::vector<uint8_t> blk;
-  const size_t bytes = lv_pack(*views, &blk, nullptr, nullptr);
-  ouro_ledger_views_dev* dv = new (std::nothrow) ouro_ledger_views_dev{dev, nullptr, {}};
+  const size_t bytes = lv_pack(*views, genesis, &blk, nullptr, nullptr, nullptr);
+  ouro_ledger_views_dev* dv =
+      new (std::nothrow) ouro_ledger_views_dev{dev, nullptr, {}, genesis != nullptr, {}};
   if (!dv) return fail(OURO_EDEVICE, "out of host memory");
   if (hipMalloc(&dv->block, bytes) != hipSuccess ||
       hipMemcpy(dv->block, blk.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
@@ -332,9 +480,13 @@ int ouro_ledger_views_upload(const ouro_ledger_views* views, ouro_ledger_views_d
     delete dv;
     return fail(OURO_EDEVICE, "ledger views: upload failed");
   }
-  lv_pack(*views, nullptr, &dv->d, static_cast<const uint8_t*>(dv->block));
+  lv_pack(*views, genesis, nullptr, &dv->d, &dv->g, static_cast<const uint8_t*>(dv->block));
   *out = dv;
   return OURO_OK;
+}
+
+int ouro_ledger_views_upload(const ouro_ledger_views* views, ouro_ledger_views_dev** out) {
+  return ouro_ledger_views_upload_overlay(views, nullptr, out);
 }
 
 void ouro_ledger_views_free(ouro_ledger_views_dev* dv) {
@@ -364,8 +516,9 @@ int ouro_tpraos_ledger_checks_device(void* stream, size_t n, const uint8_t* issu
   int dev, rc = device_state(&ds);
   if (rc || (rc = current_device(&dev))) return rc;
   if (dev != views->dev) return fail(OURO_EINVAL, "ledger views were uploaded to another device");
-  return launch_ledger(static_cast<hipStream_t>(stream), n, issuer_vk, vrf_vk, slot, leader_output,
-                       ocert_kes_period, views->d, *globals, ledger, pool_row);
+  return lv_launch(static_cast<hipStream_t>(stream), n, issuer_vk, vrf_vk, slot, leader_output,
+                   ocert_kes_period, views->d, *globals, views->has_genesis ? &views->g : nullptr,
+                   ledger, pool_row);
 }
 
 }  // extern "C"

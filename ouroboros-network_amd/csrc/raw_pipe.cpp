@@ -65,6 +65,8 @@ using namespace ouro_rt;
 // RawCall::ledger set: the views uploaded once, k_ledger_checks behind each
 // chunk's header kernel over the rows in the slot's arena (launches.h
 // launch_ledger), the OCERT counter fold in stream order as chunks drain.
+// With a genesis-delegation schedule (RawLedger::genesis) it rides in the
+// views' block and the kernel is k_ledger_checks_overlay (runtime.h lv_launch).
 namespace {
 constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kRawChunkBytes = (size_t)96 << 20;
@@ -361,9 +363,10 @@ int raw_launch_tpraos(RawSlot& s, const RawCall& c, const uint8_t* draw, size_t 
     return rc;
   uint8_t* dlv = static_cast<uint8_t*>(s.d_lv.p);
   OURO_HIP(hipStreamWaitEvent(s.st, c.ledger->uploaded, 0));
-  if ((rc = launch_ledger(s.st, mt, b.issuer_vk, b.vrf_vk, dslot, b.leader_output,
-                          b.ocert_kes_period, c.ledger->dviews, c.ledger->g, dlv + LO.bits,
-                          reinterpret_cast<uint32_t*>(dlv + LO.rows))))
+  if ((rc = lv_launch(s.st, mt, b.issuer_vk, b.vrf_vk, dslot, b.leader_output, b.ocert_kes_period,
+                      c.ledger->dviews, c.ledger->g,
+                      c.ledger->genesis ? &c.ledger->dgenesis : nullptr, dlv + LO.bits,
+                      reinterpret_cast<uint32_t*>(dlv + LO.rows))))
     return rc;
   OURO_HIP(hipMemcpyAsync(s.h_lv, dlv, LO.ctr, hipMemcpyDeviceToHost, s.st));
   OURO_HIP(hipMemcpyAsync(s.h_lv + LO.ctr, b.ocert_counter, 8 * mt, hipMemcpyDeviceToHost, s.st));
@@ -576,11 +579,12 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
   const int width = (int)knob_size(ouro_knobs::get().cbor_copy_threads, 8, 1, 64);
   if (c.env) c.env->prev = c.env->tip;
   if (c.ledger) {
-    // the views once per call, on the first slot's stream; every chunk's
-    // stream waits on the upload before its ledger kernel
+    // the views (and the genesis delegations, in the same block) once per
+    // call, on the first slot's stream; every chunk's stream waits on the
+    // upload before its ledger kernel
     if (!p.views_up) OURO_HIP(hipEventCreateWithFlags(&p.views_up, hipEventDisableTiming));
-    if ((rc = lv_upload(p.s[0].st, *c.ledger->views, &p.d_views, &c.ledger->packed,
-                        &c.ledger->dviews)))
+    if ((rc = lv_upload(p.s[0].st, *c.ledger->views, c.ledger->genesis, &p.d_views,
+                        &c.ledger->packed, &c.ledger->dviews, &c.ledger->dgenesis)))
       return rc;
     OURO_HIP(hipEventRecord(p.views_up, p.s[0].st));
     c.ledger->uploaded = p.views_up;
@@ -672,7 +676,8 @@ int raw_host_ledger(const RawCall& c) {
                                    0);
     if (rc) return fail(rc, "ouro_tpraos_pack_cbor: bad arguments");
     if ((rc = lv_host_rows(q, b.issuer_vk, b.vrf_vk, slots.data(), b.leader_output,
-                           b.ocert_kes_period, *L.views, L.g, bits.data(), rows.data())))
+                           b.ocert_kes_period, *L.views, L.g, L.genesis, bits.data(),
+                           rows.data())))
       return rc;
     for (size_t j = 0; j < q; j++) {
       if (st[j] != OURO_PACK_OK) continue;
@@ -1022,23 +1027,25 @@ namespace {
 struct LedgerArgs {
   RawLedger l{};
   LvFold fold;
-  std::vector<uint32_t> map, rows;
+  std::vector<uint32_t> map, gmap, rows;
   // the table as the call found it: a device error recomputes from it
   std::vector<uint64_t> counter0;
   std::vector<uint8_t> present0;
   ouro_ocert_counters t0{};
 };
 int ledger_call(ChainArgs* a, LedgerArgs* g, size_t n, uint64_t spkp,
-                const ouro_ledger_views* views, const ouro_ledger_globals* globals,
-                const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
-                uint8_t* ledger, uint32_t* pool_row) {
+                const ouro_ledger_views* views, const ouro_genesis_delegs* genesis,
+                const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
+                uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
   int rc;
   if ((rc = lv_views_check(views)) || (rc = lv_globals_check(globals))) return rc;
+  if (genesis && (rc = lv_genesis_check(genesis, *views))) return rc;
   if (globals->slots_per_kes_period != spkp)
     return fail(OURO_EINVAL, "globals: slots_per_kes_period differs from the call's");
   if (n && !ledger) return fail(OURO_EINVAL, "null ledger");
   if ((rc = lv_counters_check(counters, counter_out, present_out))) return rc;
   if (counters && (rc = lv_fold_map(*views, *counters, &g->map))) return rc;
+  if (counters && genesis && (rc = lv_fold_gmap(*genesis, *counters, &g->gmap))) return rc;
   try {  // (no exception crosses the C ABI)
     if (!pool_row) {
       g->rows.resize(n);
@@ -1052,13 +1059,15 @@ int ledger_call(ChainArgs* a, LedgerArgs* g, size_t n, uint64_t spkp,
     return fail(OURO_EDEVICE, "ledger call: out of host memory");
   }
   g->l.views = views;
+  g->l.genesis = genesis;
   g->l.g = *globals;
   g->l.ledger = ledger;
   g->l.pool_row = pool_row;
   if (counters) {
     g->t0 = ouro_ocert_counters{counters->m, counters->pool_id, g->counter0.data(),
                                 g->present0.data()};
-    lv_fold_begin(&g->fold, g->t0, &g->map, counter_out, present_out);
+    lv_fold_begin(&g->fold, g->t0, &g->map, genesis ? &g->gmap : nullptr, counter_out,
+                  present_out);
     g->l.fold = &g->fold;
   }
   a->c.ledger = &g->l;
@@ -1073,11 +1082,38 @@ int ledger_verify(ChainArgs* a, LedgerArgs* g) {
   const size_t per = knob_size(ouro_knobs::get().cbor_chunk, 65536, 256, (size_t)1 << 24);
   if (int rc = raw_chunks(a->c, per, &chunks)) return rc;
   return or_host(raw_run(a->c, chunks), [&] {
-    if (g->l.fold) lv_fold_begin(&g->fold, g->t0, &g->map, g->fold.counter, g->fold.present);
+    if (g->l.fold)
+      lv_fold_begin(&g->fold, g->t0, &g->map, g->fold.gmap, g->fold.counter, g->fold.present);
     return raw_host(a->c);
   });
 }
 }  // namespace
+
+int ouro_chain_validate_ledger_overlay_cbor(
+    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
+    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
+    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
+    const ouro_genesis_delegs* genesis, const ouro_ledger_globals* globals,
+    const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
+    uint8_t* ledger, uint32_t* pool_row) {
+  ChainArgs a;
+  RawEnv e{};
+  LedgerArgs g;
+  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
+                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
+                          beta_leader, eta_nonce))
+    return rc;
+  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, genesis, globals, counters,
+                           counter_out, present_out, ledger, pool_row))
+    return rc;
+  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
+                             envelope, tip_out))
+    return rc;
+  return ledger_verify(&a, &g);
+}
 
 int ouro_chain_validate_ledger_cbor(
     const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
@@ -1088,6 +1124,23 @@ int ouro_chain_validate_ledger_cbor(
     uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
     const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
     uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
+  return ouro_chain_validate_ledger_overlay_cbor(
+      raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic, epochs, eta_alpha,
+      leader_alpha, cfg, tip_in, proto, status, verdict, beta_eta, beta_leader, eta_nonce,
+      header_hash, envelope, tip_out, views, nullptr, globals, counters, counter_out, present_out,
+      ledger, pool_row);
+}
+
+int ouro_chain_validate_ledger_overlay_cbor_host(
+    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
+    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
+    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
+    const ouro_genesis_delegs* genesis, const ouro_ledger_globals* globals,
+    const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
+    uint8_t* ledger, uint32_t* pool_row) {
   ChainArgs a;
   RawEnv e{};
   LedgerArgs g;
@@ -1095,13 +1148,13 @@ int ouro_chain_validate_ledger_cbor(
                           epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
                           beta_leader, eta_nonce))
     return rc;
-  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, globals, counters, counter_out,
-                           present_out, ledger, pool_row))
+  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, genesis, globals, counters,
+                           counter_out, present_out, ledger, pool_row))
     return rc;
   if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
                              envelope, tip_out))
     return rc;
-  return ledger_verify(&a, &g);
+  return raw_verify_host(a.c);
 }
 
 int ouro_chain_validate_ledger_cbor_host(
@@ -1113,20 +1166,11 @@ int ouro_chain_validate_ledger_cbor_host(
     uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
     const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
     uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
-  ChainArgs a;
-  RawEnv e{};
-  LedgerArgs g;
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, globals, counters, counter_out,
-                           present_out, ledger, pool_row))
-    return rc;
-  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
-                             envelope, tip_out))
-    return rc;
-  return raw_verify_host(a.c);
+  return ouro_chain_validate_ledger_overlay_cbor_host(
+      raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic, epochs, eta_alpha,
+      leader_alpha, cfg, tip_in, proto, status, verdict, beta_eta, beta_leader, eta_nonce,
+      header_hash, envelope, tip_out, views, nullptr, globals, counters, counter_out, present_out,
+      ledger, pool_row);
 }
 
 // DIAGNOSTIC: the calling thread's last raw-CBOR call (ms and counts)

@@ -288,32 +288,46 @@ struct RawEnv {
 };
 // ---- the ledger-view checks (ledger_api.cpp; ledger_view.h) ----
 // the OCERT counter fold's state: the view-row -> table-index map and the
-// table being updated (the caller's counter_out / present_out)
+// table being updated (the caller's counter_out / present_out); gmap: the
+// same map for the genesis rows of a call with a genesis-delegation schedule
+// (keyed by delegate_id), or null: overlay rows are skipped
 struct LvFold {
   const std::vector<uint32_t>* map = nullptr;
+  const std::vector<uint32_t>* gmap = nullptr;
   uint64_t* counter = nullptr;
   uint8_t* present = nullptr;
 };
 int lv_views_check(const ouro_ledger_views* v);
 int lv_globals_check(const ouro_ledger_globals* g);
+int lv_genesis_check(const ouro_genesis_delegs* gd, const ouro_ledger_views& v);
 int lv_counters_check(const ouro_ocert_counters* t, const uint64_t* counter_out,
                       const uint8_t* present_out);
 int lv_host_rows(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk, const uint64_t* slot,
                  const uint8_t* leader_output, const uint64_t* c0, const ouro_ledger_views& v,
-                 const ouro_ledger_globals& g, uint8_t* ledger, uint32_t* pool_row);
-int lv_upload(hipStream_t st, const ouro_ledger_views& v, Buf* buf, std::vector<uint8_t>* host,
-              ouro_ledger_views* d);
+                 const ouro_ledger_globals& g, const ouro_genesis_delegs* gd, uint8_t* ledger,
+                 uint32_t* pool_row);
+int lv_upload(hipStream_t st, const ouro_ledger_views& v, const ouro_genesis_delegs* gd, Buf* buf,
+              std::vector<uint8_t>* host, ouro_ledger_views* d, ouro_genesis_delegs* dgd);
+int lv_launch(hipStream_t st, size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk,
+              const uint64_t* slot, const uint8_t* leader_output, const uint64_t* ocert_kes_period,
+              const ouro_ledger_views& v, const ouro_ledger_globals& g,
+              const ouro_genesis_delegs* gd, uint8_t* ledger, uint32_t* pool_row);
 int lv_fold_map(const ouro_ledger_views& v, const ouro_ocert_counters& t,
                 std::vector<uint32_t>* map);
+int lv_fold_gmap(const ouro_genesis_delegs& gd, const ouro_ocert_counters& t,
+                 std::vector<uint32_t>* gmap);
 void lv_fold_begin(LvFold* f, const ouro_ocert_counters& t, const std::vector<uint32_t>* map,
-                   uint64_t* counter_out, uint8_t* present_out);
+                   const std::vector<uint32_t>* gmap, uint64_t* counter_out, uint8_t* present_out);
 void lv_fold_run(LvFold* f, size_t n, const uint32_t* pool_row, const uint64_t* counter,
                  uint8_t* ledger);
 // What ouro_chain_validate_ledger_cbor adds to a validating call: the views
 // (uploaded once per call: dviews, `uploaded` for the chunks' streams to wait
-// on), the fold (or null) and the outputs.
+// on), the genesis-delegation schedule (or null; uploaded in the views' block:
+// dgenesis), the fold (or null) and the outputs.
 struct RawLedger {
   const ouro_ledger_views* views;
+  const ouro_genesis_delegs* genesis = nullptr;
+  ouro_genesis_delegs dgenesis{};
   ouro_ledger_globals g;
   LvFold* fold;        // null: no counters given
   uint8_t* ledger;     // OUT: n

@@ -701,7 +701,8 @@ def validate_chain_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: 
 
 
 def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_magic: int,
-                               views, globals_, *, counters=None, cfg=None, tip=None,
+                               views, globals_, *, counters=None, genesis=None, cfg=None,
+                               tip=None,
                                epochs: Optional[EpochNonces] = None,
                                eta_alpha: Optional[np.ndarray] = None,
                                leader_alpha: Optional[np.ndarray] = None, nonce: bool = False,
@@ -709,7 +710,10 @@ def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_
     """validate_chain_cbor with the ledger-view checks in the same call
     (include/ouro_verify.h ouro_chain_validate_ledger_cbor): `views` (a
     ledger.LedgerViews), `globals_` (a ledger.Globals) and optionally the OCERT
-    `counters` (a ledger.Counters) for the counter fold.  Returns
+    `counters` (a ledger.Counters) for the counter fold.  With `genesis` (a
+    ledger.GenesisDelegs; ouro_chain_validate_ledger_overlay_cbor) overlay
+    slots take the genesis-delegate branch and pool_row holds a genesis row
+    there.  Returns
     validate_chain_cbor's tuple and then (ledger, pool_row, counters_after):
     the LV_* bits (0 for a PBFT or unsliced header), each issuer's view row,
     and the table after the fold (None without counters)."""
@@ -743,11 +747,16 @@ def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_
         co, po = np.zeros_like(counters.counter), np.zeros_like(counters.present)
     lib = _native.load()
     name = "ouro_chain_validate_ledger_cbor" + ("_host" if host else "")
+    gen = ()
+    if genesis is not None:
+        name = "ouro_chain_validate_ledger_overlay_cbor" + ("_host" if host else "")
+        c_gen = genesis.c_struct()
+        gen = (ctypes.byref(c_gen),)
     rc = getattr(lib, name)(ptr(buf), buf.size, ptr(off), ptr(ln), n, slots_per_kes_period,
                             protocol_magic, e, ptr(ea), ptr(la), ctypes.byref(c_cfg),
                             ctypes.byref(t_in), ptr(proto), ptr(status), ptr(verdict), ptr(be),
                             ptr(bl), ptr(en), ptr(hh), ptr(bits), ctypes.byref(t_out),
-                            ctypes.byref(cv), ctypes.byref(cg),
+                            ctypes.byref(cv), *gen, ctypes.byref(cg),
                             None if cc is None else ctypes.byref(cc), ptr(co), ptr(po),
                             ptr(ledger), ptr(rows))
     _native.check(rc, name)

@@ -3,7 +3,11 @@
 checks with the epoch's ``LedgerView`` beside the signatures: ledger-specs'
 OVERLAY rule (the issuer is a registered pool, its VRF key is the registered
 one, its leader value is below the threshold for ITS stake) and OCERT rule (the
-certificate's KES period bounds, the per-pool counter).
+certificate's KES period bounds, the per-pool counter).  With a
+``GenesisDelegs`` schedule the OVERLAY rule's other branch runs on overlay
+slots: ``classify_overlay_slot`` (ledger-specs lookupInOverlaySchedule), the
+scheduled genesis key's delegate and its VRF key hash (pbftVrfChecks), and the
+delegate's counter.
 
 ``ledger_checks`` / ``counter_fold`` call the library (``csrc/ledger_view.h``,
 ``k_ledger_checks``, ``ouro_ocert_counter_fold``); there is no CPU fallback
@@ -14,8 +18,10 @@ tests' expected side; nothing in them comes from the library.
 
 Pinned by the reference's fixtures (tests/test_ledger_rule.py): hashKey =
 Blake2b-224 and hashVerKeyVRF = Blake2b-256.  NOT pinned by anything in the
-reference tree: isOverlaySlot's formula (ledger-specs is un-vendored) and, as
-for leader.py, checkLeaderValue.
+reference tree: isOverlaySlot's formula and classifyOverlaySlot's arithmetic
+(ledger-specs is un-vendored; the reference shows only the call and the shape
+of its result, Shelley/Protocol.hs:366-406) and, as for leader.py,
+checkLeaderValue.
 """
 from __future__ import annotations
 
@@ -32,13 +38,14 @@ import numpy as np
 
 from . import _native
 from ._native import (LV_ALL_OK, LV_BADARG, LV_COUNTER_OK, LV_KES_PERIOD_OK, LV_LEADER_OK,
-                      LV_NO_POOL, LV_OVERLAY, LV_POOL_KNOWN, LV_VRF_KEY_OK)
+                      LV_NO_POOL, LV_OVERLAY, LV_OVERLAY_ACTIVE, LV_POOL_KNOWN, LV_VRF_KEY_OK)
 from ._pack import ptr
 
-__all__ = ["LedgerViews", "Globals", "Counters", "ledger_checks", "counter_fold", "rule",
-           "fold_rule", "pool_id", "vrf_key_hash", "is_overlay_slot", "LV_ALL_OK", "LV_BADARG",
-           "LV_COUNTER_OK", "LV_KES_PERIOD_OK", "LV_LEADER_OK", "LV_NO_POOL", "LV_OVERLAY",
-           "LV_POOL_KNOWN", "LV_VRF_KEY_OK"]
+__all__ = ["LedgerViews", "Globals", "Counters", "GenesisDelegs", "GenDeleg", "ledger_checks",
+           "counter_fold", "rule", "fold_rule", "pool_id", "vrf_key_hash", "is_overlay_slot",
+           "classify_overlay_slot", "LV_ALL_OK", "LV_BADARG", "LV_COUNTER_OK", "LV_KES_PERIOD_OK",
+           "LV_LEADER_OK", "LV_NO_POOL", "LV_OVERLAY", "LV_OVERLAY_ACTIVE", "LV_POOL_KNOWN",
+           "LV_VRF_KEY_OK"]
 
 
 @dataclass(frozen=True)
@@ -148,6 +155,48 @@ class Counters:
         return c
 
 
+@dataclass(frozen=True)
+class GenDeleg:
+    """One genesis key and the GenDelegPair it maps to."""
+
+    genesis_id: bytes      # 28: hashKey of the genesis key
+    delegate_id: bytes     # 28: genDelegKeyHash, the delegate's cold key hash
+    delegate_vrf: bytes    # 32: genDelegVrfHash
+
+
+class GenesisDelegs:
+    """A genesis-delegation schedule (``ouro_genesis_delegs``): one tuple of
+    GenDeleg per view entry, sorted by genesis id here (Map.keysSet's order)
+    unless sort=False, and asc_inv = floor(1 / f)."""
+
+    def __init__(self, entries: Sequence[Sequence[GenDeleg]], asc_inv: int, sort: bool = True):
+        self.entries = [tuple(sorted(e, key=lambda x: x.genesis_id) if sort else e)
+                        for e in entries]
+        self.asc_inv = int(asc_inv)
+        k = len(self.entries)
+        rows = [x for e in self.entries for x in e]
+        self.gen_begin = np.zeros(k + 1, np.uint32)
+        for j, e in enumerate(self.entries):
+            self.gen_begin[j + 1] = self.gen_begin[j] + len(e)
+        m = max(len(rows), 1)
+        self.genesis_id = np.zeros((m, 28), np.uint8)
+        self.delegate_id = np.zeros((m, 28), np.uint8)
+        self.delegate_vrf = np.zeros((m, 32), np.uint8)
+        for r, x in enumerate(rows):
+            self.genesis_id[r] = np.frombuffer(x.genesis_id, np.uint8)
+            self.delegate_id[r] = np.frombuffer(x.delegate_id, np.uint8)
+            self.delegate_vrf[r] = np.frombuffer(x.delegate_vrf, np.uint8)
+        self.rows = len(rows)
+
+    def c_struct(self) -> _native.GenesisDelegsC:
+        return _native.GenesisDelegsC(len(self.entries), self.gen_begin.ctypes.data,
+                                      self.genesis_id.ctypes.data, self.delegate_id.ctypes.data,
+                                      self.delegate_vrf.ctypes.data, self.asc_inv)
+
+    def all_delegate_ids(self) -> List[bytes]:
+        return sorted({x.delegate_id for e in self.entries for x in e})
+
+
 def _rows(issuer_vk, vrf_vk, slot, leader_output, c0, counter):
     iv = np.ascontiguousarray(issuer_vk, np.uint8).reshape(-1, 32)
     n = iv.shape[0]
@@ -161,12 +210,14 @@ def _rows(issuer_vk, vrf_vk, slot, leader_output, c0, counter):
 
 def ledger_checks(issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, views: LedgerViews,
                   g: Globals, *, ocert_counter=None, counters: Optional[Counters] = None,
-                  host: bool = False):
+                  genesis: Optional[GenesisDelegs] = None, host: bool = False):
     """The ledger-view checks of n sliced TPraos header rows (the columns of a
     HeaderBatch / pack_cbor).  Returns (ledger, pool_row[, counters_after]):
     the LV_* bits and each issuer's view row (LV_NO_POOL: none); with
     ``counters`` (and ocert_counter) the counter fold runs too and the updated
-    table is returned.  host=True: the library's host path."""
+    table is returned.  With ``genesis`` overlay rows take the delegate branch
+    (ouro_tpraos_ledger_checks_overlay) and their pool_row is a genesis row.
+    host=True: the library's host path."""
     n, iv, vv, sl, lo, c0, ct = _rows(issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period,
                                       ocert_counter)
     ledger = np.zeros(max(n, 1), np.uint8)
@@ -177,18 +228,26 @@ def ledger_checks(issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, view
         cc = counters.c_struct()
         co, po = np.zeros_like(counters.counter), np.zeros_like(counters.present)
     name = "ouro_tpraos_ledger_checks" + ("_host" if host else "")
+    gen = ()
+    if genesis is not None:
+        name = "ouro_tpraos_ledger_checks_overlay" + ("_host" if host else "")
+        c_gen = genesis.c_struct()
+        gen = (ctypes.byref(c_gen),)
     rc = getattr(_native.load(), name)(
         n, ptr(iv), ptr(vv), ptr(sl), ptr(lo), ptr(c0), None if ct is None else ptr(ct),
-        ctypes.byref(cv), ctypes.byref(cg), None if cc is None else ctypes.byref(cc),
+        ctypes.byref(cv), *gen, ctypes.byref(cg), None if cc is None else ctypes.byref(cc),
         None if co is None else ptr(co), None if po is None else ptr(po), ptr(ledger), ptr(rows))
     _native.check(rc, name)
     out = (ledger[:n], rows[:n])
     return out + (counters.after(co, po),) if counters is not None else out
 
 
-def counter_fold(ledger, pool_row, ocert_counter, views: LedgerViews, counters: Counters):
+def counter_fold(ledger, pool_row, ocert_counter, views: LedgerViews, counters: Counters,
+                 genesis: Optional[GenesisDelegs] = None):
     """``ouro_ocert_counter_fold``: LV_COUNTER_OK into a copy of ``ledger`` in
-    stream order and the table afterwards.  Returns (ledger, counters_after)."""
+    stream order and the table afterwards; with ``genesis``
+    (``ouro_ocert_counter_fold_overlay``) the delegates' rows too.  Returns
+    (ledger, counters_after)."""
     led = np.array(ledger, np.uint8).reshape(-1)
     n = led.shape[0]
     rows = np.ascontiguousarray(pool_row, np.uint32).reshape(n)
@@ -196,10 +255,15 @@ def counter_fold(ledger, pool_row, ocert_counter, views: LedgerViews, counters: 
     cv, cc = views.c_struct(), counters.c_struct()
     co, po = np.zeros_like(counters.counter), np.zeros_like(counters.present)
     buf = led if n else np.zeros(1, np.uint8)
-    rc = _native.load().ouro_ocert_counter_fold(n, ptr(rows) if n else None,
-                                                ptr(ct) if n else None, ctypes.byref(cv),
-                                                ctypes.byref(cc), ptr(co), ptr(po), ptr(buf))
-    _native.check(rc, "ouro_ocert_counter_fold")
+    name, gen = "ouro_ocert_counter_fold", ()
+    if genesis is not None:
+        name += "_overlay"
+        c_gen = genesis.c_struct()
+        gen = (ctypes.byref(c_gen),)
+    rc = getattr(_native.load(), name)(n, ptr(rows) if n else None, ptr(ct) if n else None,
+                                       ctypes.byref(cv), *gen, ctypes.byref(cc), ptr(co), ptr(po),
+                                       ptr(buf))
+    _native.check(rc, name)
     return led, counters.after(co, po)
 
 
@@ -222,6 +286,19 @@ def is_overlay_slot(first_slot: int, d: Tuple[int, int], slot: int) -> bool:
     return ceil(s * dd) < ceil((s + 1) * dd)
 
 
+def classify_overlay_slot(first_slot: int, d: Tuple[int, int], asc_inv: int, ngen: int,
+                          slot: int) -> Optional[int]:
+    """ledger-specs classifyOverlaySlot on an overlay slot (the caller has
+    checked is_overlay_slot): None on a non-active slot, else the index of the
+    scheduled genesis key in the sorted key set -- position = ceil(s d), active
+    iff position mod ascInv == 0, index (position div ascInv) mod ngen."""
+    x = (slot - first_slot) * Fraction(d[0], d[1])
+    position = -((-x.numerator) // x.denominator)
+    if position % asc_inv != 0:
+        return None
+    return (position // asc_inv) % ngen
+
+
 def _oracle_leader():
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "oracle",
                         "leader.py")
@@ -235,8 +312,11 @@ _RES = 10**34
 
 
 def rule(views: LedgerViews, g: Globals, issuer_vk: bytes, vrf_vk: bytes, slot: int,
-         leader_output: bytes, c0: int, oracle=None) -> Tuple[int, int]:
-    """(LV_* bits without COUNTER_OK, pool_row) of one header row."""
+         leader_output: bytes, c0: int, oracle=None,
+         genesis: Optional[GenesisDelegs] = None) -> Tuple[int, int]:
+    """(LV_* bits without COUNTER_OK, pool_row) of one header row; with
+    ``genesis`` an overlay row takes the delegate branch and its row is a
+    genesis row."""
     oracle = oracle or _oracle_leader()
     bits, row = 0, LV_NO_POOL
     kp = slot // g.slots_per_kes_period
@@ -245,7 +325,20 @@ def rule(views: LedgerViews, g: Globals, issuer_vk: bytes, vrf_vk: bytes, slot: 
     j = bisect.bisect_right([e.first_slot for e in views.entries], slot) - 1
     e = views.entries[j]
     if is_overlay_slot(e.first_slot, e.d, slot):
-        return bits | LV_OVERLAY, row
+        bits |= LV_OVERLAY
+        if genesis is None:
+            return bits, row
+        gen = genesis.entries[j]
+        ix = classify_overlay_slot(e.first_slot, e.d, genesis.asc_inv, len(gen), slot)
+        if ix is None:
+            return bits, row                      # NotActiveSlotOVERLAY
+        bits |= LV_OVERLAY_ACTIVE
+        if pool_id(issuer_vk) != gen[ix].delegate_id:
+            return bits, row                      # WrongGenesisColdKeyOVERLAY
+        bits |= LV_POOL_KNOWN | LV_LEADER_OK      # (no threshold on an overlay slot)
+        if vrf_key_hash(vrf_vk) == gen[ix].delegate_vrf:
+            bits |= LV_VRF_KEY_OK                 # else WrongGenesisVRFKeyOVERLAY
+        return bits, int(genesis.gen_begin[j]) + ix
     ids = [p.pool_id for p in e.pools]
     pid = pool_id(issuer_vk)
     r = bisect.bisect_left(ids, pid)
@@ -267,16 +360,20 @@ def rule(views: LedgerViews, g: Globals, issuer_vk: bytes, vrf_vk: bytes, slot: 
 
 
 def fold_rule(views: LedgerViews, ledger: Sequence[int], pool_row: Sequence[int],
-              ocert_counter: Sequence[int], known: Dict[bytes, int]):
-    """The counter fold with a dict: (ledger with COUNTER_OK, the dict after)."""
+              ocert_counter: Sequence[int], known: Dict[bytes, int],
+              genesis: Optional[GenesisDelegs] = None):
+    """The counter fold with a dict: (ledger with COUNTER_OK, the dict after).
+    With ``genesis`` an overlay row's key is its delegate's id."""
     ids = [p.pool_id for e in views.entries for p in e.pools]
+    gids = [] if genesis is None else [x.delegate_id for e in genesis.entries for x in e]
     known = dict(known)
     out = []
     for b, r, n_i in zip(ledger, pool_row, ocert_counter):
         b = int(b)
-        if (b & LV_POOL_KNOWN) and not (b & LV_OVERLAY):
-            m0 = known.get(ids[int(r)], 0)  # currentIssueNo, "in the pool distribution"
+        if (b & LV_POOL_KNOWN) and (genesis is not None or not (b & LV_OVERLAY)):
+            key = gids[int(r)] if b & LV_OVERLAY else ids[int(r)]
+            m0 = known.get(key, 0)  # currentIssueNo: in the pool distribution / in genDelegs
             b = b | LV_COUNTER_OK if m0 <= int(n_i) else b & ~LV_COUNTER_OK
-            known[ids[int(r)]] = int(n_i)
+            known[key] = int(n_i)
         out.append(b)
     return np.array(out, np.uint8), known

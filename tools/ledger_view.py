@@ -12,7 +12,15 @@ legs (comma separated, default all):
             n TPraos headers, under 50 view entries of 3,000 pools each (the
             stream's pools among them) and a counters table
   device    k_ledger_checks alone (ouro_tpraos_ledger_checks_device) on the n
-            sliced rows resident on the device, timed with stream events"""
+            sliced rows resident on the device, timed with stream events
+  existing_ledger  ouro_chain_validate_ledger_cbor (no genesis-delegation
+            schedule): this library against the parent commit's, twice: this
+            library first in every pair, then the parent's first
+  overlay   ouro_chain_validate_ledger_overlay_cbor with a schedule (7 genesis
+            keys per entry, the stream's first pools as delegates, asc_inv = 20)
+            against ouro_chain_validate_ledger_cbor, both under d = 1/2
+  device_overlay  k_ledger_checks_overlay against k_ledger_checks on the
+            resident rows under d = 1/2"""
 import ctypes
 import json
 import os
@@ -52,7 +60,8 @@ def main():
 
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    legs = (sys.argv[3] if len(sys.argv) > 3 else "existing,ledger,device").split(",")
+    legs = (sys.argv[3] if len(sys.argv) > 3 else
+            "existing,ledger,device,existing_ledger,overlay,device_overlay").split(",")
     parent = sys.argv[4] if len(sys.argv) > 4 else None
     dev = torch.device("cuda", 0)
     lib = _native.load()
@@ -113,57 +122,102 @@ def main():
     cv, cg, cc = views.c_struct(), g.c_struct(), table.c_struct()
     co, po = np.zeros_like(table.counter), np.zeros_like(table.present)
 
-    def ledger():
-        rc = lib.ouro_chain_validate_ledger_cbor(
+    def ledger(which=lib, cv=cv, gen=None):
+        name, extra = "ouro_chain_validate_ledger_cbor", ()
+        if gen is not None:
+            name, extra = "ouro_chain_validate_ledger_overlay_cbor", (ctypes.byref(gen),)
+        rc = getattr(which, name)(
             P(s.buf), s.buf.size, P(s.off), P(s.ln), s.n, SPKP, -1, ctypes.byref(one.c_struct()),
             None, None, ctypes.byref(cfg), None, P(s.proto), P(s.st), P(s.v), P(s.be), P(s.bl),
-            None, P(s.hh), P(s.env), None, ctypes.byref(cv), ctypes.byref(cg), ctypes.byref(cc),
-            P(co), P(po), P(s.ledger), P(s.prow))
-        assert rc == 0, lib.ouro_last_error()
+            None, P(s.hh), P(s.env), None, ctypes.byref(cv), *extra, ctypes.byref(cg),
+            ctypes.byref(cc), P(co), P(po), P(s.ledger), P(s.prow))
+        assert rc == 0, which.ouro_last_error()
+
+    def hist():
+        return {hex(int(k)): int(v) for k, v in zip(*np.unique(s.ledger, return_counts=True))}
+
+    if "existing_ledger" in legs and parent:
+        old = ctypes.CDLL(parent)
+        for name in ("ouro_chain_validate_ledger_cbor", "ouro_last_error"):
+            res, args = _native.SIGNATURES[name]
+            getattr(old, name).restype, getattr(old, name).argtypes = res, args
+        tn, to = CR.alternate(ledger, lambda: ledger(old), reps)
+        report("existing_ledger", s.n, tn, to,
+               what="ouro_chain_validate_ledger_cbor: this library / the parent's")
+        # the same with the parent's call first in every pair
+        to, tn = CR.alternate(lambda: ledger(old), ledger, reps)
+        report("existing_ledger", s.n, tn, to,
+               what="ouro_chain_validate_ledger_cbor: this library / the parent's, parent first")
+
+    # the overlay legs: the same pools under d = 1/2, 7 genesis keys per entry
+    # whose delegates are the stream's first pools (their ids are in the table)
+    views_h = L.LedgerViews([L.Entry(e.first_slot, (1, 2), e.pools) for e in views.entries])
+    cvh = views_h.c_struct()
+    dl = (pools + fill)[:7]
+    gen_h = L.GenesisDelegs([tuple(L.GenDeleg(bytes([i]) * 28, p.pool_id, p.vrf_hash)
+                                   for i, p in enumerate(dl))] * ENTRIES, 20)
+    cgen = gen_h.c_struct()
+    if "overlay" in legs:
+        tn, to = CR.alternate(lambda: ledger(cv=cvh, gen=cgen), lambda: ledger(cv=cvh), reps)
+        ledger(cv=cvh, gen=cgen)
+        report("overlay", s.n, tn, to,
+               what="ouro_chain_validate_ledger_overlay_cbor / ouro_chain_validate_ledger_cbor, "
+                    "d = 1/2", genesis_keys=7, asc_inv=20, bits=hist())
 
     if "ledger" in legs:
         tn, to = CR.alternate(ledger, validate, reps)
         ledger()
-        hist = {hex(int(k)): int(v) for k, v in zip(*np.unique(s.ledger, return_counts=True))}
         report("ledger", s.n, tn, to,
                what="ouro_chain_validate_ledger_cbor / ouro_chain_validate_cbor",
-               entries=ENTRIES, pools_per_entry=POOLS, stream_pools=len(pools), bits=hist,
+               entries=ENTRIES, pools_per_entry=POOLS, stream_pools=len(pools), bits=hist(),
                all_valid=bool(((s.v & 0x3F) == 0x3F).all()),
                view_bytes=int(28 + 32 + 16) * views.rows)
 
-    if "device" in legs:
+    if "device" in legs or "device_overlay" in legs:
         d = [torch.tensor(np.ascontiguousarray(a).view(np.int64) if a.dtype == np.uint64
                           else np.ascontiguousarray(a), device=dev)
              for a in (issuer, vrf, slot, lead, c0)]
         out = torch.zeros(s.n, dtype=torch.uint8, device=dev)
         rows = torch.zeros(s.n, dtype=torch.int32, device=dev)
-        h = ctypes.c_void_p()
-        assert lib.ouro_ledger_views_upload(ctypes.byref(cv), ctypes.byref(h)) == 0
         sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-        def kern():
-            rc = lib.ouro_tpraos_ledger_checks_device(sp, s.n, *[t.data_ptr() for t in d], h,
-                                                      ctypes.byref(cg), out.data_ptr(),
-                                                      rows.data_ptr())
-            assert rc == 0, lib.ouro_last_error()
+        def kernel_leg(leg, cv, gen, **kw):
+            h = ctypes.c_void_p()
+            assert lib.ouro_ledger_views_upload_overlay(ctypes.byref(cv), gen, ctypes.byref(h)) == 0
 
-        kern()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(reps):
-            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
+            def kern():
+                rc = lib.ouro_tpraos_ledger_checks_device(sp, s.n, *[t.data_ptr() for t in d], h,
+                                                          ctypes.byref(cg), out.data_ptr(),
+                                                          rows.data_ptr())
+                assert rc == 0, lib.ouro_last_error()
+
             kern()
-            e.record()
             torch.cuda.synchronize()
-            ms.append(a.elapsed_time(e))
-        lib.ouro_ledger_views_free(h)
-        med = statistics.median(ms)
-        print(json.dumps({"leg": "device", "n": s.n, "kernel_ms": [round(x, 3) for x in ms],
-                          "kernel_median_ms": round(med, 3),
-                          "headers_per_s": round(s.n / med * 1e3),
-                          "known": int((out & 1).sum().item()),
-                          "leader_ok": int(((out & 4) != 0).sum().item())}), flush=True)
+            ms = []
+            for _ in range(reps):
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                kern()
+                e.record()
+                torch.cuda.synchronize()
+                ms.append(a.elapsed_time(e))
+            lib.ouro_ledger_views_free(h)
+            med = statistics.median(ms)
+            print(json.dumps({"leg": leg, "n": s.n, "kernel_ms": [round(x, 3) for x in ms],
+                              "kernel_median_ms": round(med, 3),
+                              "headers_per_s": round(s.n / med * 1e3),
+                              "known": int((out & 1).sum().item()),
+                              "leader_ok": int(((out & 4) != 0).sum().item()),
+                              "overlay": int(((out & 0x40) != 0).sum().item()),
+                              "overlay_active": int(((out & 0x20) != 0).sum().item()), **kw}),
+                  flush=True)
+
+        if "device" in legs:
+            kernel_leg("device", cv, None)
+        if "device_overlay" in legs:
+            kernel_leg("device_overlay", cvh, None, kernel="k_ledger_checks, d = 1/2")
+            kernel_leg("device_overlay", cvh, ctypes.byref(cgen),
+                       kernel="k_ledger_checks_overlay, d = 1/2, 7 keys, asc_inv = 20")
 
 
 if __name__ == "__main__":
