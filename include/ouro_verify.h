@@ -360,6 +360,7 @@ int ouro_tpraos_verify_batch_epochs(const ouro_tpraos_batch *b, const ouro_epoch
 #define OURO_PACK_EBB 6u    /* (Byron slicer) an epoch-boundary header: PBFT
                                checks no signature on it (PBFT.hs:327-328)     */
 #define OURO_PACK_ESHELLEY 7u /* (Byron slicer) HFC era >= 1: not a Byron header */
+#define OURO_PACK_ECAP 8u   /* (witness slicer) the block's rows pass a capacity */
 size_t ouro_tpraos_pack_bytes(size_t n);
 int ouro_tpraos_pack_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
                           const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
@@ -535,6 +536,83 @@ int ouro_block_integrity_verify_cbor_device(void *stream, const uint8_t *raw, si
                                             uint64_t slots_per_kes_period, void *arena,
                                             size_t arena_bytes, uint8_t *status, uint8_t *verdict,
                                             uint8_t *body_hash);
+
+/* Transaction key witnesses straight from raw block CBOR: the Ed25519
+ * verification of every transaction's key witnesses over its transaction id,
+ * the crypto call of ledger-specs' UTXOW rule (verifiedWits), and the largest
+ * one of a ChainDB replay.  Block i is raw[off[i] .. off[i] + len[i]) in any of
+ * the four forms of ouro_block_integrity_verify_cbor; Byron blocks are status
+ * OURO_PACK_EBYRON.  The block must be a definite array(4) that ends exactly at
+ * its span.  Item 0 (the header) and item 3 (the metadata) are skipped, not
+ * examined: ouro_block_integrity_verify_cbor checks the header.
+ *   txBodies    = [* map], definite or indefinite; tx id = Blake2b-256 of the
+ *                 element's bytes as they stand in the block
+ *   txWitnesses = [* {uint => any}], as many elements as bodies; of each map
+ *     key 0: [* [vkey: bytes(32), sig: bytes(64)]]
+ *     key 2: [* [vkey: bytes(32), sig: bytes(64), chain_code: bytes(32),
+ *                attributes]]   (bootstrap: its address check needs ledger
+ *                                state and is out of scope)
+ *     any other key: skipped; a repeated key is walked again.
+ * Witnesses are numbered in the order the walk meets them; each one's message
+ * is its transaction's 32-byte id, verified as plain Ed25519 with libsodium
+ * 1.0.18's rules (both kinds).  Rows: block i owns the tx rows
+ * [tx_begin[i], tx_begin[i + 1]) and the witness rows [wit_begin[i],
+ * wit_begin[i + 1]); a block that does not slice owns none.  A sliced block
+ * whose rows would pass a capacity (tx_begin[i] + ntx > tx_cap, or the same
+ * for witnesses) writes nothing and has status OURO_PACK_ECAP; the blocks
+ * that fit -- always a prefix of the sliced ones -- are processed in full,
+ * and tx_begin[n] / wit_begin[n] are the totals whether they fit or not.
+ * Outputs: status[i] = OURO_PACK_*; n_bad[i] = the block's witnesses that do
+ * not verify; verdict[i] = OURO_WIT_ALL_OK iff the block sliced, fit, and
+ * n_bad[i] == 0 (so also for a block without witnesses), else 0.
+ *   ouro_block_witness_count_cbor[_host]: the slicer's count pass alone:
+ *     status, ntx[i] and nwit[i] (zeros where the block does not slice) -- what
+ *     a caller sizes the capacities from.
+ *   ouro_block_witness_verify_cbor: host buffers, synchronous, on the calling
+ *     thread's stream, in consecutive groups of whole blocks under a byte
+ *     budget (OURO_WITNESS_GROUP_BYTES); a device error recomputes the call on
+ *     the host path.  Rows past the blocks that fit are left untouched.
+ *   ouro_block_witness_verify_cbor_host: the host path alone.
+ *   All four return OURO_EINVAL, before any work, for NULLs or a span outside
+ *   raw_bytes.
+ *   ouro_block_witness_verify_cbor_device: device pointers (raw as for
+ *     ouro_blake2b256_batch_device; tx_begin / wit_begin 8-byte, tx_id and
+ *     wit_vk 16-byte, wit_tx 4-byte aligned; work of
+ *     ouro_block_witness_work_bytes(n, tx_cap, wit_cap) bytes), enqueued on
+ *     `stream`, not synchronised, no host round trip between slicing and
+ *     verifying; a span outside raw_bytes is per-block status OURO_PACK_ESPAN;
+ *     rows past the blocks that fit are zero.
+ * Out of scope: the bootstrap address check and every other UTXOW rule, Byron
+ * witnesses, _multi forms, the chunked raw pipeline. */
+#define OURO_WIT_ALL_OK 0x01u
+typedef struct {
+  size_t tx_cap, wit_cap;
+  uint64_t *tx_begin, *wit_begin; /* n + 1 each; [n] = totals, also when they pass the caps */
+  uint8_t *tx_id;                 /* tx_cap x 32 */
+  uint32_t *wit_tx;               /* wit_cap: global tx row */
+  uint8_t *wit_kind, *wit_ok;     /* wit_cap each: 0 or 2; 1 = verifies */
+  uint8_t *wit_vk;                /* wit_cap x 32, may be NULL */
+} ouro_block_witness_out;
+int ouro_block_witness_count_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                  const uint32_t *len, size_t n, uint8_t *status, uint32_t *ntx,
+                                  uint32_t *nwit);
+int ouro_block_witness_count_cbor_host(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                       const uint32_t *len, size_t n, uint8_t *status,
+                                       uint32_t *ntx, uint32_t *nwit);
+int ouro_block_witness_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                   const uint32_t *len, size_t n,
+                                   const ouro_block_witness_out *out, uint8_t *status,
+                                   uint8_t *verdict, uint32_t *n_bad);
+int ouro_block_witness_verify_cbor_host(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                        const uint32_t *len, size_t n,
+                                        const ouro_block_witness_out *out, uint8_t *status,
+                                        uint8_t *verdict, uint32_t *n_bad);
+size_t ouro_block_witness_work_bytes(size_t n, size_t tx_cap, size_t wit_cap);
+int ouro_block_witness_verify_cbor_device(void *stream, const uint8_t *raw, size_t raw_bytes,
+                                          const uint64_t *off, const uint32_t *len, size_t n,
+                                          const ouro_block_witness_out *out, void *work,
+                                          size_t work_bytes, uint8_t *status, uint8_t *verdict,
+                                          uint32_t *n_bad);
 
 /* Raw Byron header CBOR -> the inputs of its PBFT block-signature check
  * (SURVEY.md §8(f) row 4).  Replaces the per-header decode + message assembly

@@ -19,6 +19,7 @@ from .ledger import (Counters, GenesisDelegs, Globals, LedgerViews, counter_fold
 from .kes import Sum6KES, kes_period
 from .tpraos import EpochNonces, HeaderBatch, first_invalid, verify_headers, verify_headers_multi
 from .vrf import PraosVRF
+from .witness import count_block_witnesses, parse_witnesses, verify_block_witnesses
 
 __all__ = [
     "ByronDSIGN",
@@ -35,6 +36,7 @@ __all__ = [
     "Sum6KES",
     "blake2b256_batch",
     "chain_envelope_cbor",
+    "count_block_witnesses",
     "counter_fold",
     "first_invalid",
     "kes_period",
@@ -43,9 +45,11 @@ __all__ = [
     "pack_byron_cbor",
     "parse_block",
     "parse_byron_header",
+    "parse_witnesses",
     "validate_chain_cbor",
     "validate_chain_ledger_cbor",
     "verify_block_integrity_cbor",
+    "verify_block_witnesses",
     "verify_byron_cbor",
     "verify_byron_headers",
     "verify_chain_cbor",

@@ -39,6 +39,9 @@ BLK_KES_OK = 0x01      # ouro_block_integrity_verify_cbor: verifyHeaderIntegrity
 BLK_BODY_OK = 0x02     # blockMatchesHeader
 BLK_ALL_OK = 0x03      # verifyBlockIntegrity
 
+PACK_ECAP = 8          # ouro_block_witness_verify_cbor status[i]: rows past a capacity
+WIT_ALL_OK = 0x01      # ... verdict[i]: every key witness of the block verifies
+
 ENV_BLOCKNO_OK = 0x01  # ouro_chain_envelope_cbor envelope[i]
 ENV_SLOT_OK = 0x02
 ENV_PREVHASH_OK = 0x04
@@ -328,6 +331,13 @@ SIGNATURES = {
                                                    _P]),
     "ouro_block_integrity_verify_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
                                                      _P, _SZ, _P, _P, _P]),
+    "ouro_block_witness_count_cbor": (_I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P]),
+    "ouro_block_witness_count_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P]),
+    "ouro_block_witness_verify_cbor": (_I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
+    "ouro_block_witness_verify_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
+    "ouro_block_witness_work_bytes": (_SZ, [_SZ, _SZ, _SZ]),
+    "ouro_block_witness_verify_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P, _SZ, _P, _P,
+                                                   _P]),
     "ouro_sum6kes_verify_batch": (_I, [_SZ, _P, _P, _P, _P, _P, _P, _P]),
     "ouro_tpraos_verify_batch": (_I, [ctypes.POINTER(TPraosBatch), _P, _P, _P]),
     "ouro_ed25519_verify_batch_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),

@@ -45,6 +45,11 @@ void load(Knobs& k) {
   read_size<size_t>(k.cbor_copy_threads, "OURO_CBOR_COPY_THREADS", 0);
   read_int(k.cbor_ramp, "OURO_CBOR_RAMP", 0);
   read_int(k.block_sort, "OURO_BLOCK_SORT", 1);
+  // the raw bytes one group of whole blocks of ouro_block_witness_verify_cbor
+  // uploads and verifies at a time (witness_api.cpp; a block larger than the
+  // budget is a group of its own); the tests force it small so that a batch
+  // spans several groups
+  read_size<size_t>(k.witness_group_bytes, "OURO_WITNESS_GROUP_BYTES", 0);
   read_int(k.lat_block, "OURO_LAT_BLOCK", 0);
   read_int(k.lat_quad, "OURO_LAT_QUAD", 1);
   read_int(k.lat_wide, "OURO_LAT_WIDE", 0xff);

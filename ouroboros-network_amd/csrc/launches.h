@@ -119,5 +119,38 @@ void launch_plan_stage(hipStream_t st, unsigned blocks, const uint4* src, uint4*
 void launch_plan_stage_ranges(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst,
                               const PlanRanges& r, uint64_t* stamp);
 
+// the transaction-witness kernels (kernels_witness.hip; cbor_witness.h), each
+// checking its own launches.  Every pointer is device memory.
+// count: status, ntx and nwit per block (zeros where it does not slice)
+int launch_witness_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
+                         const uint32_t* len, size_t n, uint8_t* status, uint32_t* ntx,
+                         uint32_t* nwit);
+// the exclusive scan of both count arrays into tx_begin / wit_begin (n + 1
+// each, [n] = the totals); sums: 2 * witness_scan_tiles(n) words of work;
+// rows[0..1] = min(total, capacity), what the later kernels read
+size_t witness_scan_tiles(size_t n);
+int launch_witness_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* nwit,
+                        uint64_t* sums, uint64_t* tx_begin, uint64_t* wit_begin, size_t tx_cap,
+                        size_t wit_cap, uint64_t* rows);
+// every row to "not written", then the emit pass of the blocks that fit
+// (status OURO_PACK_ECAP for a sliced one that does not).  tx_off / tx_len:
+// tx_cap spans for launch_blake2b; vk / sig (16-byte aligned), wit_tx, kind:
+// wit_cap rows; wit_tx = tx_base + the transaction's row
+int launch_witness_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off, const uint32_t* len,
+                        size_t n, const uint32_t* ntx, const uint32_t* nwit,
+                        const uint64_t* tx_begin, const uint64_t* wit_begin, size_t tx_cap,
+                        size_t wit_cap, uint64_t tx_base, uint64_t* tx_off, uint32_t* tx_len,
+                        uint8_t* vk, uint8_t* sig, uint32_t* wit_tx, uint8_t* kind,
+                        uint8_t* status);
+// Ed25519 per witness row over its transaction id (tx_id: tx_cap x 32, row
+// wit_tx - tx_base); the row count is read from rows[1] on the device; rows nothing was emitted to
+// and rows past the count get zeros
+int launch_witness_verify(hipStream_t st, size_t wit_cap, const uint64_t* rows, const uint8_t* vk,
+                          const uint8_t* sig, const uint32_t* wit_tx, const uint8_t* tx_id,
+                          size_t tx_cap, uint64_t tx_base, uint8_t* kind, uint8_t* wit_ok);
+int launch_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
+                          const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
+                          uint8_t* verdict, uint32_t* n_bad);
+
 }  // namespace ouro_rt
 #pragma GCC visibility pop
