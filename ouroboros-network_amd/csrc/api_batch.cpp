@@ -13,10 +13,10 @@
 #include "../../include/ouro_verify.h"
 #include "cbor.h"
 #include "host_path.h"
+#include "host_util.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launches.h"
-#include "runtime.h"
 #include "tpraos.h"
 
 using namespace ouro;
@@ -578,7 +578,8 @@ int ouro_ed25519_verify_batch_device(void* stream, size_t n, const uint8_t* pk, 
                                      const uint8_t* msg, const uint64_t* msg_off,
                                      const uint32_t* msg_len, uint8_t* verdict) {
   if (n == 0) return OURO_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_ed(st, n, pk, sig, msg, msg_off, msg_len, verdict);
 }
 
@@ -587,7 +588,8 @@ int ouro_byron_ed25519_verify_batch_device(void* stream, size_t n, const uint8_t
                                            const uint64_t* msg_off, const uint32_t* msg_len,
                                            uint8_t* verdict) {
   if (n == 0) return OURO_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_ed(st, n, pk, sig, msg, msg_off, msg_len, verdict, 1);
 }
 
@@ -595,7 +597,8 @@ int ouro_vrf03_verify_batch_device(void* stream, size_t n, const uint8_t* pk, co
                                    const uint8_t* alpha, const uint64_t* alpha_off,
                                    const uint32_t* alpha_len, uint8_t* beta, uint8_t* verdict) {
   if (n == 0) return OURO_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_vrf(st, n, pk, proof, alpha, alpha_off, alpha_len, beta, verdict);
 }
 
@@ -605,7 +608,8 @@ int ouro_vrf03_verify_batch_device_flags(void* stream, size_t n, const uint8_t* 
                                          uint8_t* beta, uint8_t* verdict, uint32_t flags) {
   if (n == 0) return OURO_OK;
   if (flags & ~OURO_VRF_STRICT_S) return fail(OURO_EINVAL, "unknown VRF flags");
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_vrf(st, n, pk, proof, alpha, alpha_off, alpha_len, beta, verdict, flags);
 }
 
@@ -614,7 +618,8 @@ int ouro_sum6kes_verify_batch_device(void* stream, size_t n, const uint8_t* vk, 
                                      const uint32_t* msg_len, const uint8_t* sig,
                                      uint8_t* verdict) {
   if (n == 0) return OURO_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_kes(st, n, vk, t, msg, msg_off, msg_len, sig, verdict);
 }
 
@@ -626,7 +631,8 @@ int ouro_tpraos_verify_batch_device(void* stream, const ouro_tpraos_batch* b, ui
   if (!verdict) return fail(OURO_EINVAL, "null verdict");
   int rc = check_hdr_batch(b);
   if (rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if ((rc = device_entry(stream, &st))) return rc;
   return launch_hdr(st, *b, verdict, beta_eta, beta_leader);
 }
 
@@ -641,10 +647,8 @@ int ouro_tpraos_pack_cbor_device(void* stream, const uint8_t* raw, size_t raw_by
   const cbor::Out o = cbor::arena_out(cbor::arena_base(arena), n, slot, era);
   cbor::batch_from(out, o, raw, n);
   if (n == 0) return OURO_OK;
-  DeviceState* ds;
-  int rc = device_state(&ds);
-  if (rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   const size_t blocks = std::min<size_t>((n + kBlock - 1) / kBlock, 4096);
   launch_tpraos_pack(st, (unsigned)blocks, raw, raw_bytes, off, len, n, slots_per_kes_period, o,
                      status);
@@ -660,7 +664,8 @@ int ouro_leader_check_batch_device(void* stream, size_t n, const uint8_t* beta,
                                    int64_t act_log_hi, uint64_t act_log_lo, int f_is_one,
                                    uint8_t* verdict) {
   if (n == 0) return OURO_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_leader(st, n, beta, sigma_num, sigma_den, act_log_hi, act_log_lo, f_is_one,
                        verdict);
 }

@@ -3,7 +3,7 @@
 // (block_launch: slicer, segment hashes, Sum6KES, finish), the host path over
 // the same batch (block_host), and the C entries.  Host code only: kernels
 // are reached through launches.h.  The host-buffer block entry runs on the
-// raw-CBOR pipeline of raw_pipe.cpp (RawKind kRawBlock).
+// raw-CBOR pipeline of raw_pipe.cpp (raw_call.h RawKind kRawBlock).
 // its own host copies of the out-of-line lane routines (common.h)
 #define OURO_NI_LINKAGE static
 #include <algorithm>
@@ -17,35 +17,16 @@
 #include "blake2b_stream.h"
 #include "cbor_block.h"
 #include "host_path.h"
+#include "host_util.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launches.h"
-#include "runtime.h"
-#include "task_pool.h"
+#include "raw_call.h"
 
 using namespace ouro;
 using namespace ouro_rt;
 
 namespace {
-
-void words_out(uint8_t* d, const uint32_t w[8]) {
-  for (int k = 0; k < 32; k++) d[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-}
-
-// [0, n) in tasks of `per` items over the library's worker pool
-template <class F>
-int host_rows(size_t n, size_t per, F work) {
-  const size_t tasks = (n + per - 1) / per;
-  if (tasks <= 1) {
-    if (n) work(0, n);
-    return OURO_OK;
-  }
-  const int width = std::max(1, ouro_host::threads_for(n));
-  const int r = ouro_pool::parallel_for(tasks, width, [&](size_t t) {
-    work(t * per, std::min(n, (t + 1) * per));
-  });
-  return r ? fail(OURO_EDEVICE, "host worker pool failed") : OURO_OK;
-}
 
 int b2b_host(size_t n, const uint8_t* msg, const uint64_t* off, const uint32_t* len,
              uint8_t* out) {
@@ -53,7 +34,7 @@ int b2b_host(size_t n, const uint8_t* msg, const uint64_t* off, const uint32_t* 
     for (size_t i = lo; i < hi; i++) {
       uint32_t d[8];
       blake2b256_stream(d, msg + off[i], len[i]);
-      words_out(out + 32 * i, d);
+      digest_bytes(out + 32 * i, d);
     }
   });
 }
@@ -62,10 +43,7 @@ int b2b_check(size_t n, const uint8_t* msg, size_t msg_bytes, const uint64_t* of
               const uint32_t* len, uint8_t* out) {
   if (!off || !len || !out) return fail(OURO_EINVAL, "null argument");
   if (!msg && msg_bytes) return fail(OURO_EINVAL, "null message buffer");
-  for (size_t i = 0; i < n; i++)  // every span before any work (checked without wrapping)
-    if (off[i] > msg_bytes || msg_bytes - off[i] < len[i])
-      return fail(OURO_EINVAL, "message " + std::to_string(i) + ": span outside msg_bytes");
-  return OURO_OK;
+  return spans_check("message", "msg_bytes", msg_bytes, off, len, n);
 }
 
 // one upload, the hash kernel and one copy-back on the calling thread's stream
@@ -150,10 +128,10 @@ int block_host(const RawCall& c) {
             blake2b256_stream(d + 8 * s, c.raw + bo.seg_off[3 * i + s], bo.seg_len[3 * i + s]);
           blake2b256_96(h, d);
           uint8_t hb[32];
-          words_out(hb, h);
+          digest_bytes(hb, h);
           ok = memcmp(hb, bo.claimed + 32 * i, 32) == 0 ? OURO_BLK_BODY_OK : 0;
         }
-        words_out(bh + 32 * i, h);
+        digest_bytes(bh + 32 * i, h);
         c.verdict[lo + i] = ok;
       }
     });
@@ -171,6 +149,19 @@ int block_host(const RawCall& c) {
 }
 
 }  // namespace ouro_rt
+
+namespace {
+// the device / _host pair once: the block kind on the raw-CBOR pipeline, or on
+// its host path alone
+int block_entry(const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len,
+                size_t n, uint64_t spkp, uint8_t* status, uint8_t* verdict, uint8_t* body_hash,
+                bool host) {
+  RawCall c = RawCall::of(kRawBlock, raw, raw_bytes, off, len, n, status, verdict);
+  c.spkp = spkp;
+  c.body_hash = body_hash;
+  return host ? raw_verify_host(c) : raw_verify(c);
+}
+}  // namespace
 
 extern "C" {
 
@@ -198,11 +189,10 @@ int ouro_blake2b256_batch_device(void* stream, size_t n, const uint8_t* msg, siz
   if (!off || !len || !out || !work || (!msg && msg_bytes))
     return fail(OURO_EINVAL, "null argument");
   if (work_bytes < ouro_blake2b256_work_bytes(n)) return fail(OURO_EINVAL, "work area too small");
-  if (reinterpret_cast<uintptr_t>(msg) & 3) return fail(OURO_EINVAL, "msg must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(out) & 15) return fail(OURO_EINVAL, "out must be 16-byte aligned");
-  DeviceState* ds;
-  if (int rc = device_state(&ds)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  if (misaligned(msg, 4)) return fail(OURO_EINVAL, "msg must be 4-byte aligned");
+  if (misaligned(out, 16)) return fail(OURO_EINVAL, "out must be 16-byte aligned");
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_blake2b(st, n, msg, msg_bytes, off, len, out, cbor::arena_base(work));
 }
 
@@ -212,20 +202,16 @@ size_t ouro_block_pack_bytes(size_t n) { return cbor::block_layout(n).total + 64
 int ouro_block_integrity_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
                                      const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
                                      uint8_t* status, uint8_t* verdict, uint8_t* body_hash) {
-  RawCall c{kRawBlock, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, nullptr,
-            nullptr, status, verdict, nullptr, nullptr, nullptr};
-  c.body_hash = body_hash;
-  return raw_verify(c);
+  return block_entry(raw, raw_bytes, off, len, n, slots_per_kes_period, status, verdict, body_hash,
+                     false);
 }
 
 int ouro_block_integrity_verify_cbor_host(const uint8_t* raw, size_t raw_bytes,
                                           const uint64_t* off, const uint32_t* len, size_t n,
                                           uint64_t slots_per_kes_period, uint8_t* status,
                                           uint8_t* verdict, uint8_t* body_hash) {
-  RawCall c{kRawBlock, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, nullptr,
-            nullptr, status, verdict, nullptr, nullptr, nullptr};
-  c.body_hash = body_hash;
-  return raw_verify_host(c);
+  return block_entry(raw, raw_bytes, off, len, n, slots_per_kes_period, status, verdict, body_hash,
+                     true);
 }
 
 int ouro_block_integrity_verify_cbor_device(void* stream, const uint8_t* raw, size_t raw_bytes,
@@ -238,11 +224,10 @@ int ouro_block_integrity_verify_cbor_device(void* stream, const uint8_t* raw, si
     return fail(OURO_EINVAL, "null argument");
   if (slots_per_kes_period == 0) return fail(OURO_EINVAL, "zero slots per KES period");
   if (arena_bytes < ouro_block_pack_bytes(n)) return fail(OURO_EINVAL, "arena too small");
-  if (reinterpret_cast<uintptr_t>(raw) & 3) return fail(OURO_EINVAL, "raw must be 4-byte aligned");
+  if (misaligned(raw, 4)) return fail(OURO_EINVAL, "raw must be 4-byte aligned");
   if (3 * n > 0xffffffffull) return fail(OURO_EINVAL, "too many blocks in one call");
-  DeviceState* ds;
-  if (int rc = device_state(&ds)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return block_launch(st, raw, raw_bytes, off, len, n, slots_per_kes_period,
                       cbor::arena_base(arena), status, verdict, body_hash);
 }

@@ -16,11 +16,10 @@
 #include "cbor.h"
 #include "cbor_byron.h"
 #include "envelope.h"
-#include "host_path.h"
+#include "host_util.h"
 #include "launch.h"
 #include "launches.h"
-#include "runtime.h"
-#include "task_pool.h"
+#include "raw_call.h"
 
 using namespace ouro;
 using namespace ouro_rt;
@@ -48,15 +47,9 @@ int env_check(EnvCall* c, const ouro_envelope_cfg* cfg, const ouro_chain_tip* ti
   if (int rc = env_args(cfg, tip_in, &c->tip)) return rc;
   c->cfg = *cfg;
   if (!host) return OURO_OK;
-  for (size_t i = 0; i < c->n; i++)
-    if (c->off[i] > c->raw_bytes || c->raw_bytes - c->off[i] < c->len[i])
-      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
+  if (int rc = spans_check("header", "raw_bytes", c->raw_bytes, c->off, c->len, c->n)) return rc;
   if (cfg->byron_epoch_slots == 0) return env_needs_epoch_slots(c->raw, c->off, c->len, c->n);
   return OURO_OK;
-}
-
-void words_out(uint8_t* d, const uint32_t w[8]) {
-  for (int k = 0; k < 32; k++) d[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
 }
 
 // one header on the host: what k_envelope_slice and k_header_hash do for it
@@ -74,7 +67,7 @@ uint8_t env_host_one(const EnvCall& c, size_t i, env::Rec* r) {
     uint32_t npre, d[8];
     const uint32_t pre = env::hash_prefix(*r, &npre);
     blake2b256_stream_prefixed(d, pre, npre, c.raw + r->hdr_off, r->hdr_len);
-    words_out(r->hash, d);
+    digest_bytes(r->hash, d);
   }
   return st;
 }
@@ -92,18 +85,13 @@ int env_host(const EnvCall& c, env::Rec* last = nullptr) {
   env::Rec prev = c.tip;
   for (size_t lo = 0; lo < c.n; lo += C) {
     const size_t m = std::min(C, c.n - lo);
-    const size_t per = 256, tasks = (m + per - 1) / per;
-    auto work = [&](size_t t) {
-      for (size_t i = t * per; i < std::min(m, (t + 1) * per); i++) {
+    const int rc = host_rows(m, 256, [&](size_t r0, size_t r1) {
+      for (size_t i = r0; i < r1; i++) {
         const uint8_t st = env_host_one(c, lo + i, &rec[i]);
         if (c.status) c.status[lo + i] = st;
       }
-    };
-    if (tasks <= 1) {
-      work(0);
-    } else if (ouro_pool::parallel_for(tasks, std::max(1, ouro_host::threads_for(m)), work)) {
-      return fail(OURO_EDEVICE, "host worker pool failed");
-    }
+    });
+    if (rc) return rc;
     for (size_t i = 0; i < m; i++) {
       c.envelope[lo + i] = env::envelope_link(prev, rec[i], c.cfg);
       memcpy(c.hash + 32 * (lo + i), rec[i].hash, 32);
@@ -115,8 +103,6 @@ int env_host(const EnvCall& c, env::Rec* last = nullptr) {
   return OURO_OK;
 }
 
-constexpr size_t a64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 // one upload, the three kernels and one copy back on the calling thread's stream
 int env_dev(const EnvCall& c) {
   hipStream_t st;
@@ -124,6 +110,7 @@ int env_dev(const EnvCall& c) {
   if (rc) return rc;
   Window w;
   if ((rc = window_of(c.n, c.off, c.len, &w))) return rc;
+  using cbor::a64;
   const size_t n = c.n;
   // the results as one block: hash | envelope | status | tip
   const size_t o_env = 32 * n, o_st = o_env + a64(n), o_tip = o_st + a64(n);
@@ -230,14 +217,11 @@ int ouro_chain_envelope_cbor_device(void* stream, const uint8_t* raw, size_t raw
   if (int rc = env_check(&c, cfg, tip_in, false)) return rc;
   if (!work || work_bytes < ouro_chain_envelope_work_bytes(n))
     return fail(OURO_EINVAL, "work area too small");
-  if (reinterpret_cast<uintptr_t>(raw) & 3) return fail(OURO_EINVAL, "raw must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(header_hash) & 15)
-    return fail(OURO_EINVAL, "header_hash must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(tip_out) & 7)
-    return fail(OURO_EINVAL, "tip_out must be 8-byte aligned");
-  DeviceState* ds;
-  if (int rc = device_state(&ds)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  if (misaligned(raw, 4)) return fail(OURO_EINVAL, "raw must be 4-byte aligned");
+  if (misaligned(header_hash, 16)) return fail(OURO_EINVAL, "header_hash must be 16-byte aligned");
+  if (misaligned(tip_out, 8)) return fail(OURO_EINVAL, "tip_out must be 8-byte aligned");
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   return launch_envelope(st, raw, raw_bytes, off, len, n, c.cfg, c.tip,
                          reinterpret_cast<env::Rec*>(cbor::arena_base(work)), status, header_hash,
                          envelope, tip_out);

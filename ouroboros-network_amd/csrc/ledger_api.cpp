@@ -11,12 +11,11 @@
 #include <vector>
 
 #include "../../include/ouro_verify.h"
-#include "host_path.h"
+#include "host_util.h"
 #include "launch.h"
 #include "launches.h"
 #include "ledger_view.h"
-#include "runtime.h"
-#include "task_pool.h"
+#include "raw_call.h"
 
 using namespace ouro;
 using namespace ouro_rt;
@@ -30,8 +29,6 @@ struct ouro_ledger_views_dev {
 };
 
 namespace {
-constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int cmp28(const uint8_t* a, const uint8_t* b) { return memcmp(a, b, 28); }
 
 // the rows of a (checked) schedule packed as one block; *d: the same schedule
@@ -257,21 +254,14 @@ int lv_host_rows(size_t n, const uint8_t* issuer_vk, const uint8_t* vrf_vk, cons
                  const uint8_t* leader_output, const uint64_t* c0, const ouro_ledger_views& v,
                  const ouro_ledger_globals& g, const ouro_genesis_delegs* gd, uint8_t* ledger,
                  uint32_t* pool_row) {
-  const size_t per = 256, tasks = (n + per - 1) / per;
-  auto work = [&](size_t t) {
-    for (size_t i = t * per; i < std::min(n, (t + 1) * per); i++)
+  return host_rows(n, 256, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++)
       ledger[i] = gd ? lv::ledger_check_lane<true>(v, g, *gd, issuer_vk + 32 * i, vrf_vk + 32 * i,
                                                    slot[i], leader_output + 64 * i, c0[i],
                                                    &pool_row[i])
                      : lv::ledger_check_lane(v, g, issuer_vk + 32 * i, vrf_vk + 32 * i, slot[i],
                                              leader_output + 64 * i, c0[i], &pool_row[i]);
-  };
-  if (tasks <= 1) {
-    if (tasks) work(0);
-  } else if (ouro_pool::parallel_for(tasks, std::max(1, ouro_host::threads_for(n)), work)) {
-    return fail(OURO_EDEVICE, "host worker pool failed");
-  }
-  return OURO_OK;
+  });
 }
 
 // a checked schedule (and genesis-delegation schedule, or null) packed and
@@ -507,10 +497,9 @@ int ouro_tpraos_ledger_checks_device(void* stream, size_t n, const uint8_t* issu
   const RowArgs r{n, issuer_vk, vrf_vk, slot, leader_output, ocert_kes_period, nullptr};
   if (int rc = rows_check(r, ledger, false)) return rc;
   if (!pool_row) return fail(OURO_EINVAL, "null pool_row");
-  if ((reinterpret_cast<uintptr_t>(issuer_vk) | reinterpret_cast<uintptr_t>(vrf_vk) |
-       reinterpret_cast<uintptr_t>(pool_row)) & 3)
+  if (misaligned(issuer_vk, 4) || misaligned(vrf_vk, 4) || misaligned(pool_row, 4))
     return fail(OURO_EINVAL, "issuer_vk, vrf_vk and pool_row must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(slot) | reinterpret_cast<uintptr_t>(ocert_kes_period)) & 7)
+  if (misaligned(slot, 8) || misaligned(ocert_kes_period, 8))
     return fail(OURO_EINVAL, "slot and ocert_kes_period must be 8-byte aligned");
   DeviceState* ds;
   int dev, rc = device_state(&ds);

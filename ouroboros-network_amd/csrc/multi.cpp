@@ -1,5 +1,7 @@
 // multi.cpp -- one process, several GPUs: the per-device worker pool and the
-// *_multi entries, the device count and NUMA entries.  Host code only.
+// *_multi entries (the raw-CBOR ones shard a raw_call.h RawCall over
+// raw_pipe.cpp's raw_verify), the device count and NUMA entries.  Host code
+// only.
 // its own host copies of the out-of-line lane routines (common.h)
 #define OURO_NI_LINKAGE static
 #include <algorithm>
@@ -13,7 +15,8 @@
 #include <vector>
 
 #include "../../include/ouro_verify.h"
-#include "runtime.h"
+#include "host_util.h"
+#include "raw_call.h"
 
 using namespace ouro_rt;
 
@@ -220,13 +223,16 @@ RawCall raw_shard(const RawCall& c, size_t lo, size_t m) {
 int raw_verify_multi(const RawCall& c, const int* devices, int ndev) {
   if (c.n == 0) return OURO_OK;
   if (int rc0 = raw_check(c)) return rc0;
-  for (size_t i = 0; i < c.n; i++)  // every span inside raw before any shard starts
-    if (c.off[i] > c.raw_bytes || c.raw_bytes - c.off[i] < c.len[i])
-      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
+  // every span inside raw before any shard starts: the shards do not look again
+  if (int rc = spans_check("header", "raw_bytes", c.raw_bytes, c.off, c.len, c.n)) return rc;
   std::vector<int> devs;
   int rc = multi_devices(devices, ndev, &devs);
   if (rc) return rc;
-  return run_multi(devs, c.n, [&](size_t lo, size_t m) { return raw_verify(raw_shard(c, lo, m)); });
+  RawCall checked = c;
+  checked.spans_checked = true;
+  return run_multi(devs, c.n, [&](size_t lo, size_t m) {
+    return raw_verify(raw_shard(checked, lo, m));
+  });
 }
 }  // namespace
 
@@ -294,8 +300,14 @@ int ouro_tpraos_verify_cbor_multi(const int* devices, int ndev, const uint8_t* r
   if (n && slots_per_kes_period == 0) return fail(OURO_EINVAL, "zero slots per KES period");
   if ((eta_alpha == nullptr) != (leader_alpha == nullptr))
     return fail(OURO_EINVAL, "give both VRF input arrays or neither");
-  RawCall c{kRawHdr, raw, raw_bytes, off, len, n, slots_per_kes_period, epoch_nonce, eta_alpha,
-            leader_alpha, status, verdict, beta_eta, beta_leader, eta_nonce};
+  RawCall c = RawCall::of(kRawHdr, raw, raw_bytes, off, len, n, status, verdict);
+  c.spkp = slots_per_kes_period;
+  c.eta0 = epoch_nonce;
+  c.ea = eta_alpha;
+  c.la = leader_alpha;
+  c.be = beta_eta;
+  c.bl = beta_leader;
+  c.nonce = eta_nonce;
   return raw_verify_multi(c, devices, ndev);
 }
 
@@ -304,12 +316,12 @@ int ouro_integrity_verify_cbor_multi(const int* devices, int ndev, const uint8_t
                                      size_t n, uint64_t slots_per_kes_period, uint8_t* status,
                                      uint8_t* verdict) {
   if (n && slots_per_kes_period == 0) return fail(OURO_EINVAL, "zero slots per KES period");
-  RawCall c{kRawKes, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, nullptr,
-            nullptr, status, verdict, nullptr, nullptr, nullptr};
+  RawCall c = RawCall::of(kRawKes, raw, raw_bytes, off, len, n, status, verdict);
+  c.spkp = slots_per_kes_period;
   return raw_verify_multi(c, devices, ndev);
 }
 
-// The combined entry (raw_pipe.cpp ouro_chain_verify_cbor) sharded like the
+// The combined entry (chain_api.cpp ouro_chain_verify_cbor) sharded like the
 // others: each shard classifies and verifies its own headers; the epoch
 // schedule is validated and packed once and shared by every shard.
 int ouro_chain_verify_cbor_multi(const int* devices, int ndev, const uint8_t* raw,
@@ -319,9 +331,15 @@ int ouro_chain_verify_cbor_multi(const int* devices, int ndev, const uint8_t* ra
                                  const uint8_t* leader_alpha, uint8_t* proto, uint8_t* status,
                                  uint8_t* verdict, uint8_t* beta_eta, uint8_t* beta_leader,
                                  uint8_t* eta_nonce) {
-  RawCall c{kRawChain, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, eta_alpha,
-            leader_alpha, status, verdict, beta_eta, beta_leader, eta_nonce, protocol_magic,
-            proto};
+  RawCall c = RawCall::of(kRawChain, raw, raw_bytes, off, len, n, status, verdict);
+  c.spkp = slots_per_kes_period;
+  c.ea = eta_alpha;
+  c.la = leader_alpha;
+  c.be = beta_eta;
+  c.bl = beta_leader;
+  c.nonce = eta_nonce;
+  c.magic = protocol_magic;
+  c.proto = proto;
   if (n == 0) return OURO_OK;
   std::vector<uint64_t> tab;
   if (epochs) {
@@ -338,8 +356,8 @@ int ouro_byron_verify_cbor_multi(const int* devices, int ndev, const uint8_t* ra
                                  uint8_t* verdict) {
   if (protocol_magic < -1 || protocol_magic > (int64_t)0xffffffffll)
     return fail(OURO_EINVAL, "protocol magic outside Word32 (or -1)");
-  RawCall c{kRawByron, raw, raw_bytes, off, len, n, 0, nullptr, nullptr, nullptr, status,
-            verdict, nullptr, nullptr, nullptr, protocol_magic};
+  RawCall c = RawCall::of(kRawByron, raw, raw_bytes, off, len, n, status, verdict);
+  c.magic = protocol_magic;
   return raw_verify_multi(c, devices, ndev);
 }
 

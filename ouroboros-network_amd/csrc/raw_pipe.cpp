@@ -1,27 +1,24 @@
 // raw_pipe.cpp -- raw header CBOR in host memory -> verdicts in one call: the
-// chunked multi-slot pipeline (raw_run), its host-path recompute, and the
-// *_verify_cbor entries.  Host code only: kernels are reached through
-// launches.h.
+// engine, a chunked multi-slot pipeline (raw_run) behind raw_verify.  Its
+// host-path recompute is raw_host.cpp, the *_verify_cbor entries over it are
+// chain_api.cpp.  Host code only: kernels are reached through launches.h.
 // its own host copies of the out-of-line lane routines (common.h)
 #define OURO_NI_LINKAGE static
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstring>
-#include <memory>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "../../include/ouro_verify.h"
 #include "cbor.h"
 #include "cbor_byron.h"
-#include "host_path.h"
+#include "host_util.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launches.h"
-#include "runtime.h"
-#include "task_pool.h"
+#include "raw_call.h"
 
 using namespace ouro;
 using namespace ouro_rt;
@@ -51,7 +48,7 @@ using namespace ouro_rt;
 //     the uploads and the other slots' kernels overlap, and the kernels of
 //     neighbouring chunks share the CUs as each one's waves retire.
 // A device error stops the pipeline (everything in flight is waited for) and
-// the whole batch is recomputed on the host path (raw_host).
+// the whole batch is recomputed on the host path (raw_host.cpp raw_host).
 // The combined entry (kRawChain, ouro_chain_verify_cbor) classifies every
 // header while it is gathered (cbor.h era_class): a chunk of one era runs that
 // era's path above, a mixed chunk both slicers and both kernels on its one
@@ -66,12 +63,11 @@ using namespace ouro_rt;
 // chunk's header kernel over the rows in the slot's arena (launches.h
 // launch_ledger), the OCERT counter fold in stream order as chunks drain.
 // With a genesis-delegation schedule (RawLedger::genesis) it rides in the
-// views' block and the kernel is k_ledger_checks_overlay (runtime.h lv_launch).
+// views' block and the kernel is k_ledger_checks_overlay (raw_call.h lv_launch).
 namespace {
-constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr size_t kRawChunkBytes = (size_t)96 << 20;
 
-// (RawKind, RawCall: runtime.h)
+// (RawKind, RawCall: raw_call.h)
 struct RawChunk {
   size_t lo, m, bytes;
 };
@@ -161,7 +157,6 @@ RawLvOut raw_lv_out(size_t mt) {
   return l;
 }
 
-// Every span inside raw (as ouro_tpraos_pack_cbor demands), and the chunks.
 // a raw-CBOR knob (knobs.h; 0 = unset) if inside [lo, hi], else the default
 size_t knob_size(const std::atomic<size_t>& k, size_t dflt, size_t lo, size_t hi) {
   const size_t v = k.load(std::memory_order_relaxed);
@@ -182,21 +177,28 @@ size_t raw_chunk_target(size_t j, size_t left, size_t per, bool ramp) {
   return std::max<size_t>(t, 256);
 }
 
+// The chunks of a call, and on the way every span inside raw (as
+// ouro_tpraos_pack_cbor demands) unless the entry has checked them: one pass
+// over off / len per call either way.
 int raw_chunks(const RawCall& c, size_t per, std::vector<RawChunk>* out) {
   out->clear();
   const bool ramp = ouro_knobs::get().cbor_ramp.load(std::memory_order_relaxed) == 1;
+  // (locals: the loop runs once per header, and *out growing may not alias them)
+  const bool check = !c.spans_checked;
+  const size_t n = c.n, raw_bytes = c.raw_bytes;
+  const uint64_t* off = c.off;
+  const uint32_t* len = c.len;
   RawChunk k{0, 0, 0};
-  size_t target = raw_chunk_target(0, c.n, per, ramp);
-  for (size_t i = 0; i < c.n; i++) {
-    if (c.off[i] > c.raw_bytes || c.raw_bytes - c.off[i] < c.len[i])
-      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
-    if (k.m && (k.m >= target || k.bytes + c.len[i] > kRawChunkBytes)) {
+  size_t target = raw_chunk_target(0, n, per, ramp);
+  for (size_t i = 0; i < n; i++) {
+    if (check && !span_inside(raw_bytes, off[i], len[i])) return span_fail("header", "raw_bytes", i);
+    if (k.m && (k.m >= target || k.bytes + len[i] > kRawChunkBytes)) {
       out->push_back(k);
       k = RawChunk{i, 0, 0};
-      target = raw_chunk_target(out->size(), c.n - i, per, ramp);
+      target = raw_chunk_target(out->size(), n - i, per, ramp);
     }
     k.m++;
-    k.bytes += c.len[i];
+    k.bytes += len[i];
   }
   if (k.m) out->push_back(k);
   return OURO_OK;
@@ -579,6 +581,7 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
   const int width = (int)knob_size(ouro_knobs::get().cbor_copy_threads, 8, 1, 64);
   if (c.env) c.env->prev = c.env->tip;
   if (c.ledger) {
+    c.ledger->fold_begin();
     // the views (and the genesis delegations, in the same block) once per
     // call, on the first slot's stream; every chunk's stream waits on the
     // upload before its ledger kernel
@@ -620,194 +623,6 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
   return rc;
 }
 
-// the host path over the same batch: host slicer + host verification, in
-// chunks (no batch-sized arena), results straight into the caller's buffers
-int raw_host_byron(const RawCall& c) {
-  const size_t C = 1 << 16;
-  for (size_t lo = 0; lo < c.n; lo += C) {
-    const size_t m = std::min(C, c.n - lo);
-    const size_t nb = ouro_byron_pack_bytes(m, c.len + lo);
-    std::unique_ptr<uint8_t[]> arena(new (std::nothrow) uint8_t[nb]);  // every row written
-    if (!arena) return fail(OURO_EDEVICE, "raw Byron host path: out of host memory");
-    ouro_byron_batch b;
-    int rc = ouro_byron_pack_cbor(c.raw, c.raw_bytes, c.off + lo, c.len + lo, m, c.magic,
-                                  arena.get(), nb, &b, c.status + lo, 0);
-    if (rc) return fail(rc, "ouro_byron_pack_cbor: bad arguments");
-    if ((rc = ouro_host::ed_batch(m, b.pk, b.sig, b.msg, b.msg_off, b.msg_len, c.verdict + lo, 1)))
-      return fail(rc, "raw Byron host path failed");
-    for (size_t i = lo; i < lo + m; i++)
-      c.verdict[i] = c.status[i] == OURO_PACK_EBB ? 1
-                                                  : (c.status[i] == OURO_PACK_OK && c.verdict[i]);
-  }
-  return OURO_OK;
-}
-
-int raw_host(const RawCall& c);
-
-// a ledger call on the host path: the TPraos headers sliced again on the host
-// in chunks, ledger_check_lane over their rows, the fold in stream order
-// (c.proto and c.status are the chain kind's, already written)
-int raw_host_ledger(const RawCall& c) {
-  RawLedger& L = *c.ledger;
-  const size_t C = 1 << 16;
-  std::vector<uint32_t> ix, rows;
-  std::vector<uint64_t> off, slots;
-  std::vector<uint32_t> len;
-  std::vector<uint8_t> st, bits, arena;
-  for (size_t lo = 0; lo < c.n; lo += C) {
-    const size_t m = std::min(C, c.n - lo);
-    memset(L.ledger + lo, 0, m);
-    ix.clear();
-    for (size_t i = lo; i < lo + m; i++) {
-      L.pool_row[i] = OURO_LV_NO_POOL;
-      if (c.proto[i] == OURO_PROTO_TPRAOS) ix.push_back((uint32_t)(i - lo));
-    }
-    const size_t q = ix.size();
-    if (!q) continue;
-    off.resize(q), len.resize(q), slots.resize(q), st.resize(q), bits.resize(q), rows.resize(q);
-    for (size_t j = 0; j < q; j++) {
-      off[j] = c.off[lo + ix[j]];
-      len[j] = c.len[lo + ix[j]];
-    }
-    arena.resize(ouro_tpraos_pack_bytes(q));
-    ouro_tpraos_batch b{};
-    int rc = ouro_tpraos_pack_cbor(c.raw, c.raw_bytes, off.data(), len.data(), q, c.spkp,
-                                   arena.data(), arena.size(), &b, slots.data(), nullptr, st.data(),
-                                   0);
-    if (rc) return fail(rc, "ouro_tpraos_pack_cbor: bad arguments");
-    if ((rc = lv_host_rows(q, b.issuer_vk, b.vrf_vk, slots.data(), b.leader_output,
-                           b.ocert_kes_period, *L.views, L.g, L.genesis, bits.data(),
-                           rows.data())))
-      return rc;
-    for (size_t j = 0; j < q; j++) {
-      if (st[j] != OURO_PACK_OK) continue;
-      const size_t i = lo + ix[j];
-      L.ledger[i] = bits[j];
-      L.pool_row[i] = rows[j];
-      if (L.fold) lv_fold_run(L.fold, 1, &rows[j], &b.ocert_counter[j], &L.ledger[i]);
-    }
-  }
-  return OURO_OK;
-}
-
-// The combined entry on the host path: per chunk of 64 K headers the same
-// partition as a mixed device chunk -- each class's offset / length (and
-// alpha) list through its own host slicer and verification, both result sets
-// scattered back to the caller's order.
-int raw_host_chain(const RawCall& c) {
-  const size_t C = 1 << 16;
-  std::vector<uint32_t> idx[2];
-  std::vector<uint64_t> off;
-  std::vector<uint32_t> len;
-  std::vector<uint8_t> st, v, be, bl, en, ea, la;
-  for (size_t lo = 0; lo < c.n; lo += C) {
-    const size_t m = std::min(C, c.n - lo);
-    idx[0].clear();
-    idx[1].clear();
-    for (size_t i = lo; i < lo + m; i++) {  // (every span was checked before any work)
-      c.proto[i] = (uint8_t)cbor::era_class(c.raw + c.off[i], c.len[i]);
-      idx[c.proto[i] == OURO_PROTO_TPRAOS ? 1 : 0].push_back((uint32_t)(i - lo));
-    }
-    for (int cls = 0; cls < 2; cls++) {
-      const std::vector<uint32_t>& ix = idx[cls];
-      const size_t q = ix.size();
-      if (!q) continue;
-      off.resize(q);
-      len.resize(q);
-      st.assign(q, 0);
-      v.assign(q, 0);
-      for (size_t j = 0; j < q; j++) {
-        off[j] = c.off[lo + ix[j]];
-        len[j] = c.len[lo + ix[j]];
-      }
-      RawCall sub{cls ? kRawHdr : kRawByron, c.raw, c.raw_bytes, off.data(), len.data(), q,
-                  c.spkp, nullptr, nullptr, nullptr, st.data(), v.data(), nullptr, nullptr,
-                  nullptr, c.magic};
-      if (cls) {
-        if (c.ea) {
-          ea.resize(32 * q);
-          la.resize(32 * q);
-          for (size_t j = 0; j < q; j++) {
-            memcpy(&ea[32 * j], c.ea + 32 * (lo + ix[j]), 32);
-            memcpy(&la[32 * j], c.la + 32 * (lo + ix[j]), 32);
-          }
-          sub.ea = ea.data();
-          sub.la = la.data();
-        }
-        sub.epochs = c.epochs;
-        sub.epochs_bytes = c.epochs_bytes;
-        if (c.be) be.assign(64 * q, 0), sub.be = be.data();
-        if (c.bl) bl.assign(64 * q, 0), sub.bl = bl.data();
-        if (c.nonce) en.assign(32 * q, 0), sub.nonce = en.data();
-      }
-      const int rc = raw_host(sub);
-      if (rc) return rc;
-      for (size_t j = 0; j < q; j++) {
-        const size_t i = lo + ix[j];
-        c.status[i] = st[j];
-        c.verdict[i] = v[j];
-        // (a PBFT header has no VRF outputs: zero rows)
-        if (c.be) cls ? memcpy(c.be + 64 * i, &be[64 * j], 64) : memset(c.be + 64 * i, 0, 64);
-        if (c.bl) cls ? memcpy(c.bl + 64 * i, &bl[64 * j], 64) : memset(c.bl + 64 * i, 0, 64);
-        if (c.nonce) cls ? memcpy(c.nonce + 32 * i, &en[32 * j], 32) : memset(c.nonce + 32 * i, 0, 32);
-      }
-    }
-  }
-  return OURO_OK;
-}
-
-int raw_host(const RawCall& c) {
-  if (c.kind == kRawByron) return raw_host_byron(c);
-  if (c.kind == kRawBlock) return block_host(c);
-  if (c.kind == kRawChain) {
-    try {  // (its lists are vectors; no exception crosses the C ABI)
-      if (int rc = raw_host_chain(c)) return rc;
-      if (c.ledger)
-        if (int rc = raw_host_ledger(c)) return rc;
-      if (!c.env) return OURO_OK;
-      // a validating call: the envelope with the host build of the same routines
-      if (int rc = env_host_run(c.raw, c.off, c.len, c.n, c.env->cfg, c.env->tip, nullptr,
-                                c.env->hash, c.env->envelope, &c.env->prev))
-        return rc;
-      if (c.env->tip_out) env::tip_of_rec(c.env->tip_out, c.env->prev);
-      return OURO_OK;
-    } catch (const std::bad_alloc&) {
-      return fail(OURO_EDEVICE, "raw CBOR host path: out of host memory");
-    }
-  }
-  const size_t C = 1 << 16;
-  const size_t cap = std::min(C, c.n);
-  const size_t nb = ouro_tpraos_pack_bytes(cap);
-  std::unique_ptr<uint8_t[]> arena(new (std::nothrow) uint8_t[nb]);
-  std::unique_ptr<uint64_t[]> slots(new (std::nothrow) uint64_t[cap]);
-  if (!arena || !slots) return fail(OURO_EDEVICE, "raw CBOR host path: out of host memory");
-  for (size_t lo = 0; lo < c.n; lo += C) {
-    const size_t m = std::min(C, c.n - lo);
-    ouro_tpraos_batch b{};  // (the slicer sets the required members only)
-    int rc = ouro_tpraos_pack_cbor(c.raw, c.raw_bytes, c.off + lo, c.len + lo, m, c.spkp,
-                                   arena.get(), nb, &b, slots.get(), nullptr, c.status + lo, 0);
-    if (rc) return fail(rc, "ouro_tpraos_pack_cbor: bad arguments");
-    if (c.kind == kRawKes) {
-      rc = ouro_host::kes_batch(m, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig,
-                                c.verdict + lo);
-    } else {
-      if (c.ea) {
-        b.eta_alpha = c.ea + 32 * lo;
-        b.leader_alpha = c.la + 32 * lo;
-      } else {
-        b.slot = slots.get();
-        b.epoch_nonce = c.eta0;
-      }
-      if (c.nonce) b.eta_nonce = c.nonce + 32 * lo;
-      rc = ouro_host::hdr_batch(&b, c.verdict + lo, c.be ? c.be + 64 * lo : nullptr,
-                                c.bl ? c.bl + 64 * lo : nullptr, c.ea ? nullptr : c.epochs);
-    }
-    if (rc) return fail(rc, "raw CBOR host path failed");
-    for (size_t i = lo; i < lo + m; i++)
-      if (c.status[i] != OURO_PACK_OK) c.verdict[i] = 0;
-  }
-  return OURO_OK;
-}
 }  // namespace
 
 namespace ouro_rt {
@@ -829,9 +644,9 @@ int raw_check(const RawCall& c) {
 int raw_verify_host(const RawCall& c) {
   if (c.n == 0) return OURO_OK;
   if (int rc = raw_check(c)) return rc;
-  for (size_t i = 0; i < c.n; i++)  // every span before any output is written
-    if (c.off[i] > c.raw_bytes || c.raw_bytes - c.off[i] < c.len[i])
-      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
+  // every span before any output is written
+  if (!c.spans_checked)
+    if (int rc = spans_check("header", "raw_bytes", c.raw_bytes, c.off, c.len, c.n)) return rc;
   return raw_host(c);
 }
 
@@ -847,356 +662,10 @@ int raw_verify(const RawCall& c) {
 }  // namespace ouro_rt
 
 extern "C" {
-
-// ---- storage integrity (KES only) over raw headers ----
-// verifyHeaderIntegrity (ouroboros-consensus-shelley/src/Ouroboros/Consensus/
-// Shelley/Ledger/Integrity.hs:20-44): Sum6KES of the raw header body under the
-// opcert's hot key at t = kesPeriod(slot) - c0 (0 below c0) -- the check the
-// VolatileDB parser runs on every block at open
-// (ouroboros-consensus/src/Ouroboros/Consensus/Storage/VolatileDB/Impl/Parser.hs:66-85)
-// and ImmutableDB chunk validation on every block of a chunk
-// (.../ImmutableDB/Impl/Validation.hs:358-365).  The raw-CBOR pipeline above:
-// the device slicer (cbor.h, kes_t_of = Integrity.hs:38-44), then the Sum6KES
-// kernel on its rows; a header the slicer rejects is 0.
-int ouro_integrity_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                               const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
-                               uint8_t* status, uint8_t* verdict) {
-  RawCall c{kRawKes, raw, raw_bytes, off, len, n, slots_per_kes_period, nullptr, nullptr,
-            nullptr, status, verdict, nullptr, nullptr, nullptr};
-  return raw_verify(c);
-}
-
-// Raw TPraos headers -> the full header check (ouroboros-consensus-shelley/
-// src/Ouroboros/Consensus/Shelley/Protocol.hs:433-442 over each decoded
-// header) in one call through the raw-CBOR pipeline above.
-int ouro_tpraos_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                            const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
-                            const uint8_t* epoch_nonce, const uint8_t* eta_alpha,
-                            const uint8_t* leader_alpha, uint8_t* status, uint8_t* verdict,
-                            uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce) {
-  RawCall c{kRawHdr, raw, raw_bytes, off, len, n, slots_per_kes_period, epoch_nonce, eta_alpha,
-            leader_alpha, status, verdict, beta_eta, beta_leader, eta_nonce};
-  return raw_verify(c);
-}
-
-// Raw Byron headers -> PBFT's block-signature verdicts (ouroboros-consensus/
-// src/Ouroboros/Consensus/Protocol/PBFT.hs:332-338; the storage integrity
-// check ouroboros-consensus-byron/src/Ouroboros/Consensus/Byron/Ledger/
-// Integrity.hs:24-35) through the raw-CBOR pipeline above: chunks gathered
-// into pinned NUMA-local staging, the device Byron slicer (k_byron_pack, the
-// host slicer's cbor_byron.h parse), then the Ed25519 kernel with ByronDSIGN
-// acceptance, five chunks in flight.  An epoch-boundary header is 1 (status
-// OURO_PACK_EBB); a rejected one 0.
-int ouro_byron_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                           const uint32_t* len, size_t n, int64_t protocol_magic,
-                           uint8_t* status, uint8_t* verdict) {
-  RawCall c{kRawByron, raw, raw_bytes, off, len, n, 0, nullptr, nullptr, nullptr, status,
-            verdict, nullptr, nullptr, nullptr, protocol_magic};
-  return raw_verify(c);
-}
-
-// A raw header stream across eras and epochs in one call (include/
-// ouro_verify.h): every header classified (cbor.h era_class) while the
-// pipeline gathers it, PBFT headers through the Byron slicer + ByronDSIGN
-// kernel, TPraos headers through the TPraos slicer + header kernel with mkSeed
-// under the epoch schedule, a mixed chunk through both on one upload.
-namespace {
-struct ChainArgs {
-  RawCall c;
-  std::vector<uint64_t> tab;
-};
-int chain_call(ChainArgs* a, const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-               const uint32_t* len, size_t n, uint64_t spkp, int64_t magic,
-               const ouro_epoch_nonces* epochs, const uint8_t* ea, const uint8_t* la,
-               uint8_t* proto, uint8_t* status, uint8_t* verdict, uint8_t* be, uint8_t* bl,
-               uint8_t* nonce) {
-  a->c = RawCall{kRawChain, raw, raw_bytes, off, len, n, spkp, nullptr, ea, la, status,
-                 verdict, be, bl, nonce, magic, proto};
-  if (n == 0) return OURO_OK;
-  if (epochs) {
-    if (int rc = epoch_tab_build(epochs, &a->tab)) return rc;
-    a->c.epochs = reinterpret_cast<const uint8_t*>(a->tab.data());
-    a->c.epochs_bytes = 8 * a->tab.size();
-  }
-  return raw_check(a->c);
-}
-}  // namespace
-
-int ouro_chain_verify_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                           const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
-                           int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-                           const uint8_t* eta_alpha, const uint8_t* leader_alpha, uint8_t* proto,
-                           uint8_t* status, uint8_t* verdict, uint8_t* beta_eta,
-                           uint8_t* beta_leader, uint8_t* eta_nonce) {
-  ChainArgs a;
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  return raw_verify(a.c);
-}
-
-int ouro_chain_verify_cbor_host(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                                const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
-                                int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-                                const uint8_t* eta_alpha, const uint8_t* leader_alpha,
-                                uint8_t* proto, uint8_t* status, uint8_t* verdict,
-                                uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce) {
-  ChainArgs a;
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  return raw_verify_host(a.c);
-}
-
-// validateHeader's two halves over a raw chain in one call (ouroboros-consensus/
-// src/Ouroboros/Consensus/HeaderValidation.hs:413-432): the chain kind's crypto
-// as ouro_chain_verify_cbor runs it, and per chunk, on the same stream and over
-// the bytes already uploaded, the envelope kernels (RawCall env).
-namespace {
-int validate_call(ChainArgs* a, RawEnv* e, const uint8_t* raw, size_t raw_bytes,
-                  const uint64_t* off, const uint32_t* len, size_t n,
-                  const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in,
-                  uint8_t* header_hash, uint8_t* envelope, ouro_chain_tip* tip_out) {
-  if (int rc = env_args(cfg, tip_in, &e->tip)) return rc;
-  if (n == 0) {  // nothing to link: the checked tip passes through
-    if (tip_out) env::tip_of_rec(tip_out, e->tip);
-    return OURO_OK;
-  }
-  if (!header_hash || !envelope) return fail(OURO_EINVAL, "null header_hash or envelope");
-  e->cfg = *cfg;
-  e->prev = e->tip;
-  e->hash = header_hash;
-  e->envelope = envelope;
-  e->tip_out = tip_out;
-  a->c.env = e;
-  for (size_t i = 0; i < n; i++)  // every span before anything runs
-    if (off[i] > raw_bytes || raw_bytes - off[i] < len[i])
-      return fail(OURO_EINVAL, "header " + std::to_string(i) + ": span outside raw_bytes");
-  if (cfg->byron_epoch_slots == 0) return env_needs_epoch_slots(raw, off, len, n);
-  return OURO_OK;
-}
-}  // namespace
-
-int ouro_chain_validate_cbor(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                             const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
-                             int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-                             const uint8_t* eta_alpha, const uint8_t* leader_alpha,
-                             const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in,
-                             uint8_t* proto, uint8_t* status, uint8_t* verdict, uint8_t* beta_eta,
-                             uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
-                             uint8_t* envelope, ouro_chain_tip* tip_out) {
-  ChainArgs a;
-  RawEnv e{};
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
-                             envelope, tip_out))
-    return rc;
-  return raw_verify(a.c);
-}
-
-int ouro_chain_validate_cbor_host(const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
-                                  const uint32_t* len, size_t n, uint64_t slots_per_kes_period,
-                                  int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-                                  const uint8_t* eta_alpha, const uint8_t* leader_alpha,
-                                  const ouro_envelope_cfg* cfg, const ouro_chain_tip* tip_in,
-                                  uint8_t* proto, uint8_t* status, uint8_t* verdict,
-                                  uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce,
-                                  uint8_t* header_hash, uint8_t* envelope,
-                                  ouro_chain_tip* tip_out) {
-  ChainArgs a;
-  RawEnv e{};
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
-                             envelope, tip_out))
-    return rc;
-  return raw_verify_host(a.c);
-}
-
-// validateHeader with the ledger-view checks of SL.updateChainDepState
-// (Shelley/Protocol.hs:433-442; ledger-specs OVERLAY and OCERT) in the same
-// call: the validating call above with RawCall ledger set.
-namespace {
-struct LedgerArgs {
-  RawLedger l{};
-  LvFold fold;
-  std::vector<uint32_t> map, gmap, rows;
-  // the table as the call found it: a device error recomputes from it
-  std::vector<uint64_t> counter0;
-  std::vector<uint8_t> present0;
-  ouro_ocert_counters t0{};
-};
-int ledger_call(ChainArgs* a, LedgerArgs* g, size_t n, uint64_t spkp,
-                const ouro_ledger_views* views, const ouro_genesis_delegs* genesis,
-                const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
-                uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
-  int rc;
-  if ((rc = lv_views_check(views)) || (rc = lv_globals_check(globals))) return rc;
-  if (genesis && (rc = lv_genesis_check(genesis, *views))) return rc;
-  if (globals->slots_per_kes_period != spkp)
-    return fail(OURO_EINVAL, "globals: slots_per_kes_period differs from the call's");
-  if (n && !ledger) return fail(OURO_EINVAL, "null ledger");
-  if ((rc = lv_counters_check(counters, counter_out, present_out))) return rc;
-  if (counters && (rc = lv_fold_map(*views, *counters, &g->map))) return rc;
-  if (counters && genesis && (rc = lv_fold_gmap(*genesis, *counters, &g->gmap))) return rc;
-  try {  // (no exception crosses the C ABI)
-    if (!pool_row) {
-      g->rows.resize(n);
-      pool_row = g->rows.data();
-    }
-    if (counters) {
-      g->counter0.assign(counters->counter, counters->counter + counters->m);
-      g->present0.assign(counters->present, counters->present + counters->m);
-    }
-  } catch (const std::bad_alloc&) {
-    return fail(OURO_EDEVICE, "ledger call: out of host memory");
-  }
-  g->l.views = views;
-  g->l.genesis = genesis;
-  g->l.g = *globals;
-  g->l.ledger = ledger;
-  g->l.pool_row = pool_row;
-  if (counters) {
-    g->t0 = ouro_ocert_counters{counters->m, counters->pool_id, g->counter0.data(),
-                                g->present0.data()};
-    lv_fold_begin(&g->fold, g->t0, &g->map, genesis ? &g->gmap : nullptr, counter_out,
-                  present_out);
-    g->l.fold = &g->fold;
-  }
-  a->c.ledger = &g->l;
-  return OURO_OK;
-}
-// the device pipeline, or after a device error the host path from the
-// table as the call found it (the pipeline's fold may have moved it)
-int ledger_verify(ChainArgs* a, LedgerArgs* g) {
-  if (a->c.n == 0) return OURO_OK;
-  if (int rc0 = raw_check(a->c)) return rc0;
-  std::vector<RawChunk> chunks;
-  const size_t per = knob_size(ouro_knobs::get().cbor_chunk, 65536, 256, (size_t)1 << 24);
-  if (int rc = raw_chunks(a->c, per, &chunks)) return rc;
-  return or_host(raw_run(a->c, chunks), [&] {
-    if (g->l.fold)
-      lv_fold_begin(&g->fold, g->t0, &g->map, g->fold.gmap, g->fold.counter, g->fold.present);
-    return raw_host(a->c);
-  });
-}
-}  // namespace
-
-int ouro_chain_validate_ledger_overlay_cbor(
-    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
-    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
-    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
-    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
-    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
-    const ouro_genesis_delegs* genesis, const ouro_ledger_globals* globals,
-    const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
-    uint8_t* ledger, uint32_t* pool_row) {
-  ChainArgs a;
-  RawEnv e{};
-  LedgerArgs g;
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, genesis, globals, counters,
-                           counter_out, present_out, ledger, pool_row))
-    return rc;
-  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
-                             envelope, tip_out))
-    return rc;
-  return ledger_verify(&a, &g);
-}
-
-int ouro_chain_validate_ledger_cbor(
-    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
-    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
-    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
-    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
-    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
-    const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
-    uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
-  return ouro_chain_validate_ledger_overlay_cbor(
-      raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic, epochs, eta_alpha,
-      leader_alpha, cfg, tip_in, proto, status, verdict, beta_eta, beta_leader, eta_nonce,
-      header_hash, envelope, tip_out, views, nullptr, globals, counters, counter_out, present_out,
-      ledger, pool_row);
-}
-
-int ouro_chain_validate_ledger_overlay_cbor_host(
-    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
-    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
-    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
-    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
-    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
-    const ouro_genesis_delegs* genesis, const ouro_ledger_globals* globals,
-    const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
-    uint8_t* ledger, uint32_t* pool_row) {
-  ChainArgs a;
-  RawEnv e{};
-  LedgerArgs g;
-  if (int rc = chain_call(&a, raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic,
-                          epochs, eta_alpha, leader_alpha, proto, status, verdict, beta_eta,
-                          beta_leader, eta_nonce))
-    return rc;
-  if (int rc = ledger_call(&a, &g, n, slots_per_kes_period, views, genesis, globals, counters,
-                           counter_out, present_out, ledger, pool_row))
-    return rc;
-  if (int rc = validate_call(&a, &e, raw, raw_bytes, off, len, n, cfg, tip_in, header_hash,
-                             envelope, tip_out))
-    return rc;
-  return raw_verify_host(a.c);
-}
-
-int ouro_chain_validate_ledger_cbor_host(
-    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
-    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
-    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
-    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
-    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
-    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
-    const ouro_ledger_globals* globals, const ouro_ocert_counters* counters,
-    uint64_t* counter_out, uint8_t* present_out, uint8_t* ledger, uint32_t* pool_row) {
-  return ouro_chain_validate_ledger_overlay_cbor_host(
-      raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic, epochs, eta_alpha,
-      leader_alpha, cfg, tip_in, proto, status, verdict, beta_eta, beta_leader, eta_nonce,
-      header_hash, envelope, tip_out, views, nullptr, globals, counters, counter_out, present_out,
-      ledger, pool_row);
-}
-
 // DIAGNOSTIC: the calling thread's last raw-CBOR call (ms and counts)
 int ouro_debug_cbor_stats(double* out6) {
   if (!out6) return fail(OURO_EINVAL, "null buffer");
   memcpy(out6, t_raw_stats, sizeof t_raw_stats);
   return OURO_OK;
 }
-
-// The same on raw headers already in device memory (raw, off, len, arena,
-// status, verdict: device pointers; arena >= ouro_tpraos_pack_bytes(n)):
-// the device slicer and the Sum6KES kernel enqueued on `stream`, not
-// synchronised.  A rejected header's zeroed row (OURO_PACK_*) cannot verify.
-int ouro_integrity_verify_cbor_device(void* stream, const uint8_t* raw, size_t raw_bytes,
-                                      const uint64_t* off, const uint32_t* len, size_t n,
-                                      uint64_t slots_per_kes_period, void* arena,
-                                      size_t arena_bytes, uint8_t* status, uint8_t* verdict) {
-  if (n == 0) return OURO_OK;
-  if (!verdict) return fail(OURO_EINVAL, "null verdict");
-  ouro_tpraos_batch b{};
-  int rc = ouro_tpraos_pack_cbor_device(stream, raw, raw_bytes, off, len, n,
-                                        slots_per_kes_period, arena, arena_bytes, &b, nullptr,
-                                        nullptr, status);
-  if (rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return launch_kes(st, n, b.hot_vk, b.kes_t, b.body, b.body_off, b.body_len, b.kes_sig, verdict);
-}
-
 }  // extern "C"

@@ -16,11 +16,10 @@
 #include "cbor_block.h"
 #include "cbor_witness.h"
 #include "host_path.h"
+#include "host_util.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launches.h"
-#include "runtime.h"
-#include "task_pool.h"
 
 using namespace ouro;
 using namespace ouro_rt;
@@ -29,21 +28,6 @@ namespace {
 
 using Out = ouro_block_witness_out;
 constexpr size_t kGroupBytes = (size_t)256 << 20;  // OURO_WITNESS_GROUP_BYTES' default
-
-// [0, n) in tasks of `per` items over the library's worker pool
-template <class F>
-int host_rows(size_t n, size_t per, F work) {
-  const size_t tasks = (n + per - 1) / per;
-  if (tasks <= 1) {
-    if (n) work(0, n);
-    return OURO_OK;
-  }
-  const int width = std::max(1, ouro_host::threads_for(n));
-  const int r = ouro_pool::parallel_for(tasks, width, [&](size_t t) {
-    work(t * per, std::min(n, (t + 1) * per));
-  });
-  return r ? fail(OURO_EDEVICE, "host worker pool failed") : OURO_OK;
-}
 
 // the work of one device sequence: counts, the scan's tile sums and row
 // counts, the tx spans, the witness keys and signatures, the hash work area
@@ -114,13 +98,10 @@ int wit_rows(hipStream_t st, const uint8_t* draw, size_t raw_bytes, const uint64
 }
 
 // ---- argument checks ----
-int spans_check(const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len,
-                size_t n) {
+int blocks_check(const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len,
+                 size_t n) {
   if (!off || !len || (!raw && raw_bytes)) return fail(OURO_EINVAL, "null argument");
-  for (size_t i = 0; i < n; i++)  // every span before any work (checked without wrapping)
-    if (off[i] > raw_bytes || raw_bytes - off[i] < len[i])
-      return fail(OURO_EINVAL, "block " + std::to_string(i) + ": span outside raw_bytes");
-  return OURO_OK;
+  return spans_check("block", "raw_bytes", raw_bytes, off, len, n);
 }
 int out_check(const Out* o) {
   if (!o || !o->tx_begin || !o->wit_begin) return fail(OURO_EINVAL, "null argument");
@@ -187,7 +168,7 @@ int wit_host(const uint8_t* raw, const uint64_t* off, const uint32_t* len, size_
          for (size_t r = lo; r < hi; r++) {
            uint32_t d[8];
            blake2b256_stream(d, raw + tx_off[r], tx_len[r]);
-           for (int k = 0; k < 32; k++) o.tx_id[32 * r + k] = (uint8_t)(d[k >> 2] >> (8 * (k & 3)));
+           digest_bytes(o.tx_id + 32 * r, d);
          }
        })))
     return rc;
@@ -375,7 +356,7 @@ int verify_call(const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const
     return OURO_OK;
   }
   if (!status || !verdict || !n_bad) return fail(OURO_EINVAL, "null argument");
-  if (int rc = spans_check(raw, raw_bytes, off, len, n)) return rc;
+  if (int rc = blocks_check(raw, raw_bytes, off, len, n)) return rc;
   auto on_host = [&] { return wit_host(raw, off, len, n, *out, status, verdict, n_bad); };
   return host ? on_host() : or_host(wit_dev(raw, off, len, n, *out, status, verdict, n_bad), on_host);
 }
@@ -384,7 +365,7 @@ int count_call(const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const 
                size_t n, uint8_t* status, uint32_t* ntx, uint32_t* nwit, bool host) {
   if (n == 0) return OURO_OK;
   if (!status || !ntx || !nwit) return fail(OURO_EINVAL, "null argument");
-  if (int rc = spans_check(raw, raw_bytes, off, len, n)) return rc;
+  if (int rc = blocks_check(raw, raw_bytes, off, len, n)) return rc;
   auto on_host = [&] { return count_host(raw, off, len, n, status, ntx, nwit); };
   return host ? on_host() : or_host(count_dev(raw, off, len, n, status, ntx, nwit), on_host);
 }
@@ -434,18 +415,15 @@ int ouro_block_witness_verify_cbor_device(void* stream, const uint8_t* raw, size
     return fail(OURO_EINVAL, "null argument");
   if (work_bytes < ouro_block_witness_work_bytes(n, out->tx_cap, out->wit_cap))
     return fail(OURO_EINVAL, "work area too small");
-  if (reinterpret_cast<uintptr_t>(raw) & 3) return fail(OURO_EINVAL, "raw must be 4-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(out->tx_begin) | reinterpret_cast<uintptr_t>(out->wit_begin) |
-       reinterpret_cast<uintptr_t>(off)) & 7)
+  if (misaligned(raw, 4)) return fail(OURO_EINVAL, "raw must be 4-byte aligned");
+  if (misaligned(out->tx_begin, 8) || misaligned(out->wit_begin, 8) || misaligned(off, 8))
     return fail(OURO_EINVAL, "off, tx_begin and wit_begin must be 8-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(out->tx_id) | reinterpret_cast<uintptr_t>(out->wit_vk)) & 15)
+  if (misaligned(out->tx_id, 16) || misaligned(out->wit_vk, 16))
     return fail(OURO_EINVAL, "tx_id and wit_vk must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(out->wit_tx) | reinterpret_cast<uintptr_t>(n_bad) |
-       reinterpret_cast<uintptr_t>(len)) & 3)
+  if (misaligned(out->wit_tx, 4) || misaligned(n_bad, 4) || misaligned(len, 4))
     return fail(OURO_EINVAL, "len, wit_tx and n_bad must be 4-byte aligned");
-  DeviceState* ds;
-  if (int rc = device_state(&ds)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  hipStream_t st;
+  if (int rc = device_entry(stream, &st)) return rc;
   uint8_t* a = cbor::arena_base(work);
   const WitLayout l = wit_layout(n, out->tx_cap, out->wit_cap);
   WitDev d;

@@ -268,13 +268,28 @@ def test_no_getenv_on_call_paths():
     variable could switch kernels between calls).  numa.cpp's sysfs root and
     the task pool's size are read once at their first use (function-local
     statics), the opt-in shims' error mode once per process."""
-    csrc = os.path.join(ROOT, "ouroboros-network_amd", "csrc")
-    kernel_units = ["kernels.hip", "kernels_lat.hip"]
-    product = kernel_units + ["host_path.hip", "pack.cpp", "runtime.cpp", "api_batch.cpp",
-                              "raw_pipe.cpp", "plan.cpp", "multi.cpp", "byron_dlg.cpp"]
-    # numa.cpp and task_pool.cpp each read one variable once, at first use (the
-    # docstring's exceptions): product units, but not held to the getenv rule
-    read_once = ["numa.cpp", "task_pool.cpp"]
+    import subprocess
+
+    pkg = os.path.join(ROOT, "ouroboros-network_amd")
+    csrc = os.path.join(pkg, "csrc")
+    # the product's units are the Makefile's own: every source a from-scratch
+    # build of the library compiles (a dry run prints the commands), a kernel
+    # unit being a .hip compiled for the device as well
+    dry = subprocess.run(["make", "-C", pkg, "-n", "-B", "lib/libouro_verify.so"],
+                         capture_output=True, text=True, check=True).stdout
+    compiled = [(m.group(1), "--offload-host-only" not in line and m.group(1).endswith(".hip"))
+                for line in dry.splitlines()
+                for m in [re.search(r" -c -o \S+\.o csrc/(\S+\.(?:cpp|hip))", line)] if m]
+    link = [line for line in dry.splitlines() if "-shared" in line]
+    assert len(link) == 1 and len(re.findall(r"\S+\.o\b", link[0])) == len(compiled) >= 20
+    kernel_units = sorted({f for f, device in compiled if device})
+    assert len(kernel_units) >= 4
+    # numa.cpp and task_pool.cpp each read one variable once, at first use, and
+    # knobs.cpp is where the switches are read (the docstring's exceptions):
+    # product units, but not held to the getenv rule
+    read_once = ["numa.cpp", "task_pool.cpp", "knobs.cpp"]
+    product = sorted({f for f, _ in compiled} - set(read_once))
+    assert not set(read_once) - {f for f, _ in compiled}
     src = {f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())
            for f in product + read_once}
     for f in product:
