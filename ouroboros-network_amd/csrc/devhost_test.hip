@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "blake2b_stream.h"
+#include "lane_items.h"
 #include "leader.h"
 #include "ledger_view.h"
 #include "tpraos.h"
@@ -79,6 +80,16 @@ void fe_to_bytes(uint8_t* out, const fe& f) {
   uint32_t w[8];
   fe_to_words(w, f);
   memcpy(out, w, 32);
+}
+// the fixed-record items of lane_items.h in a host loop
+template <int kOp>
+int lt_host_op(int op, int n, const uint32_t* in, uint32_t* out, int param) {
+  if (op == kOp) {
+    for (int i = 0; i < n; i++) lt::item<kOp>(in + (size_t)i * lt::kIn, out + (size_t)i * lt::kOut, param);
+    return 0;
+  }
+  if constexpr (kOp + 1 < lt::kOps) return lt_host_op<kOp + 1>(op, n, in, out, param);
+  return -1;
 }
 }  // namespace
 
@@ -441,6 +452,56 @@ int dh_tpraos_verify(const ouro_tpraos_batch* b, int mode, uint8_t* verdict, uin
     }
     if (mode) hdr_combine_split(r);
     hdr_finish_item(*b, i, opts, r, lanes[0].s, verdict, beta_eta, beta_leader);
+  }
+  return 0;
+}
+
+// ---- lane_items.h on the host: the entries of csrc/lane_test.hip (lt_*), same
+// records, same items, run in a loop (tests/test_lane_exact.py, backend
+// "host").  0, or -1 on bad arguments.  `stride` places items on the device's
+// threads and means nothing here: wave_max_small is the identity on the host.
+int dh_lt_op(int op, int n, const uint32_t* in, uint32_t* out, int param) {
+  if (n <= 0 || !in || !out) return -1;
+  return lt_host_op<0>(op, n, in, out, param);
+}
+int dh_lt_sha512(int n, const uint8_t* pre, const uint8_t* buf, size_t buflen, const uint32_t* off,
+                 const uint32_t* len, uint8_t* out) {
+  if (n <= 0 || !pre || !buf || !off || !len || !out) return -1;
+  for (int i = 0; i < n; i++) {
+    if ((size_t)off[i] + len[i] > buflen) return -1;
+    uint32_t p[16], w[16];
+    for (int k = 0; k < 16; k++) p[k] = ld_le32(pre + 64 * (size_t)i + 4 * k);
+    lt::sha512_item(p, buf + off[i], len[i], w);
+    memcpy(out + 64 * (size_t)i, w, 64);
+  }
+  return 0;
+}
+// variant 1: the pre phase, the chain from the cfg word it left, the finish --
+// the split header kernel's schedule (the host has one dsm_lane)
+int dh_lt_ed(int n, int stride, int variant, const uint32_t* in, uint32_t* out) {
+  if (n <= 0 || stride <= 0 || !in || !out) return -1;
+  for (int i = 0; i < n; i++) {
+    Lane lane;
+    uint32_t* o = out + (size_t)i * lt::kChainOut;
+    lt::ed_setup(in + (size_t)i * lt::kEdIn, o, lane.s, host_btab(), variant ? kPhasePre : kPhaseAll);
+    if (variant) dsm_lane(lane.s, host_btab(), (uint32_t)*lane.s.word(kSlotCfg));
+    lt::chain_finish(o, lane.s);
+  }
+  return 0;
+}
+int dh_lt_u(int n, int stride, const uint32_t* in, uint32_t* out) {
+  if (n <= 0 || stride <= 0 || !in || !out) return -1;
+  for (int i = 0; i < n; i++) {
+    Lane lane;
+    lt::u_item(in + (size_t)i * lt::kUIn, out + (size_t)i * lt::kChainOut, lane.s, host_btab());
+  }
+  return 0;
+}
+int dh_lt_v(int n, int stride, const uint32_t* in, uint32_t* out) {
+  if (n <= 0 || stride <= 0 || !in || !out) return -1;
+  for (int i = 0; i < n; i++) {
+    Lane lane;
+    lt::v_item(in + (size_t)i * lt::kVIn, out + (size_t)i * lt::kChainOut, lane.s, host_btab());
   }
   return 0;
 }

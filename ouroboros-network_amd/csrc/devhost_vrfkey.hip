@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "lane_items.h"
 #include "tpraos.h"
 #include "vrfkey_ws.h"
 
@@ -119,5 +120,30 @@ size_t dh_vrfkey_layout(size_t n, size_t budget, size_t* out7) {
   const size_t v[7] = {L.kmax, L.cap, L.off_rep, L.off_uniq, L.off_kidx, L.off_flag, L.group_bytes};
   memcpy(out7, v, sizeof v);
   return L.table_bytes;
+}
+
+// lane_items.h's table U on the host (csrc/lane_test.hip lt_u_table): the
+// per-key pass and the fill of every window for each of nkeys keys, then item
+// i from the table of key kidx[i] with the c and s of its 80-byte proof.
+// 0, or -1 on bad arguments.
+int dh_lt_u_table(int nkeys, const uint8_t* keys, int n, const uint32_t* kidx,
+                  const uint8_t* proofs, int stride, uint32_t* out) {
+  if (nkeys <= 0 || n <= 0 || stride <= 0 || !keys || !kidx || !proofs || !out) return -1;
+  std::vector<int32_t> tabs((size_t)nkeys * kYKeyWords), base(kYBaseWords);
+  std::vector<uint8_t> flag(nkeys);
+  for (int k = 0; k < nkeys; k++)
+    flag[k] = (uint8_t)dh_vrfkey_build(keys + 32 * (size_t)k, tabs.data() + (size_t)k * kYKeyWords,
+                                       base.data());
+  ouro_tpraos_batch b{};
+  b.n = (size_t)n;
+  b.eta_proof = proofs;
+  for (int i = 0; i < n; i++) {
+    if (kidx[i] >= (uint32_t)nkeys) return -1;
+    Lane lane;
+    std::vector<int32_t> res(kResWords + 4, 0);
+    lt::u_table_item(b, (size_t)i, flag[kidx[i]] != 0, out + (size_t)i * lt::kChainOut, lane.s,
+                     Slot{res.data()}, host_ubtab(), tabs.data() + (size_t)kidx[i] * kYKeyWords);
+  }
+  return 0;
 }
 }

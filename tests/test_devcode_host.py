@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import hdr_cases as HC
+import lane_vectors as LV
 import oracle_ffi as O
 from edge_cases import ed25519_edge_cases, vrf_edge_cases
 
@@ -43,7 +44,7 @@ def dec(b):
 def test_field_ops(dh):
     rng = np.random.default_rng(0)
     out = ctypes.create_string_buffer(32)
-    specials = [0, 1, 2, P - 1, P - 2, 19, 2**255 - 20, 2**254, (P - 1) // 2]
+    specials = LV.FIELD_SPECIALS
     vals = specials + [int.from_bytes(rng.bytes(32), "little") % P for _ in range(300)]
     for i, x in enumerate(vals):
         y = vals[(7 * i + 3) % len(vals)]
@@ -63,8 +64,7 @@ def test_invert_vartime(dh):
     random canonical values, values >= p and unreduced limb vectors."""
     rng = np.random.default_rng(5)
     out = ctypes.create_string_buffer(32)
-    specials = [0, 1, 2, 3, 19, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2**254, 2**255 - 20,
-                2**128 - 1, 2**30, 2**30 - 1, 2**240 + 1, 5**100 % P]
+    specials = LV.INVERT_SPECIALS
     vals = specials + [int.from_bytes(rng.bytes(32), "little") % P for _ in range(3000)]
     vals += [int.from_bytes(rng.bytes(32), "little") >> int(rng.integers(0, 250))
              for _ in range(500)]
@@ -112,8 +112,7 @@ def test_table_entry_packing(dh):
     E = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
     words = (ctypes.c_uint32 * 8)()
     back = (ctypes.c_uint32 * 10)()
-    cases = [[(1 << 28) - 1] * 10, [0] * 10, [(1 << 26) - 1, (1 << 25) - 1] * 5,
-             [1 << 26, 1 << 25] * 5, [(1 << 26) - 19] + [(1 << 25) - 1, (1 << 26) - 1] * 4 + [(1 << 25) - 1]]
+    cases = [list(c) for c in LV.PACKING_CASES]
     for _ in range(2000):
         top = int(rng.choice([1 << 25, 1 << 26, 1 << 27, 1 << 28]))
         cases.append([int(rng.integers(0, top)) for _ in range(10)])
@@ -131,8 +130,7 @@ def test_table_entry_packing(dh):
 def test_scalar_reduce(dh):
     rng = np.random.default_rng(2)
     out = ctypes.create_string_buffer(32)
-    for v in [b"\xff" * 64, bytes(64), L.to_bytes(64, "little"), (L - 1).to_bytes(64, "little"),
-              (2 * L).to_bytes(64, "little")] + [rng.bytes(64) for _ in range(200)]:
+    for v in LV.REDUCE_INPUTS + [rng.bytes(64) for _ in range(200)]:
         dh.dh_sc_reduce64(out, v)
         assert dec(out.raw) == dec(v) % L
 
@@ -174,8 +172,7 @@ def test_half_scalars_v2_equals_v1(dh):
     breaks as the round-1 step, so the pairs are identical bit for bit: on
     structured values and 20,000 random h < 2^253 (uniform, and below L)."""
     rng = np.random.default_rng(21)
-    hs = [0, 1, 2, 3, 8, L - 1, L - 2, 2**252, 2**253 - 1, 2**128, 2**128 + 1, 2**127,
-          (L - 1) // 2, 8 * 3**80 % L, 2**200 + 7, 2**129 - 1, 3 * 2**160 + 5]
+    hs = list(LV.HALF_HS)
     hs += [int.from_bytes(rng.bytes(32), "little") >> 3 for _ in range(10000)]
     hs += [int.from_bytes(rng.bytes(64), "little") % L for _ in range(10000)]
     bufs = [ctypes.create_string_buffer(32) for _ in range(4)]

@@ -14,19 +14,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from lane_vectors import NON_CANONICAL, NO_DECODE, SMALL_ORDER
+from lane_vectors import directed as _directed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "ouroboros-network_amd", "lib", "libouro_devhost_test.so")
 L = 2**252 + 27742317777372353535851937790883648493
 P = 2**255 - 19
-# the order-8 y coordinate (csrc/ge25519.h ge_has_small_order)
-Y8 = int.from_bytes(np.array([0x8f95e826, 0xb027b2c2, 0x89f4c345, 0xf098eff2, 0x05acdfd5,
-                              0x3933c6d3, 0x880238b1, 0x05fc536d], np.uint32).tobytes(), "little")
-SMALL_ORDER = [(1).to_bytes(32, "little"), (P - 1).to_bytes(32, "little"),
-               bytes(32), bytes(31) + b"\x80",
-               Y8.to_bytes(32, "little"), (Y8 | 1 << 255).to_bytes(32, "little"),
-               (P - Y8).to_bytes(32, "little"), ((P - Y8) | 1 << 255).to_bytes(32, "little")]
-NON_CANONICAL = b"\xff" * 31 + b"\x7f"   # y = 2^255 - 1 >= p
-NO_DECODE = b"\x02" + bytes(31)          # y = 2: (y^2 - 1) / (d y^2 + 1) is not a square
 
 
 class Lib:
@@ -76,17 +70,6 @@ def _valid_keys(dh, rng, count):
         if dh.u_inline(pk, 1, 1)[0]:
             keys.append(pk)
     return keys
-
-
-def _directed(width):
-    """c where carries ripple, where a digit is exactly +-2^(w-1) or zero, and
-    where the top window takes the carry."""
-    m = (1 << 128) - 1
-    half = 1 << (width - 1)
-    rep = lambda d: sum(d << (width * k) for k in range(128 // width + 1)) & m  # noqa: E731
-    return [0, 1, m, int.from_bytes(b"\x80" * 16, "little"), int.from_bytes(b"\x7f" * 16, "little"),
-            int.from_bytes(b"\x81" * 16, "little"), int.from_bytes(b"\x00\xff" * 8, "little"),
-            rep(half), rep(half - 1), rep(half + 1)]
 
 
 def test_table_shape(dh):
