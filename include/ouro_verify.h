@@ -230,15 +230,18 @@ int ouro_sum6kes_verify_batch(size_t n, const uint8_t *vk /* n x 32 */,
  * ocert_sigma -- equality over all of them, never a hash alone -- and runs the
  * Ed25519 check once per distinct record; the verdict bits are the ones a
  * check per header gives (Ed25519 verification is a pure function of key,
- * message and signature).  The grouping is redone inside every call; nothing
- * is cached between calls.  A batch of mostly distinct certificates (more
- * than 7/8 of n) runs the check per header as before.  OURO_OCERT_SHARE=0 in
+ * message and signature).  The verdict of each distinct record is kept per
+ * stream for the next calls (OURO_KEY_CACHE, below), so a call verifies only
+ * the records its stream has not seen.  A batch of mostly distinct certificates
+ * (more than 7/8 of n) runs the check per header as before and keeps nothing.  OURO_OCERT_SHARE=0 in
  * the environment turns the sharing off.  The latency plans and the host path
  * never share.
  * Footprint: the workspace belongs to the calling thread's pooled context, is
  * kept per stream for its next call and grows with the largest batch seen:
  * 4 x (the next power of two >= 2n) + 9n bytes, about 17 MB at 1M headers and
- * 1.1 MB per 65,536-header chunk of the pipelined paths.
+ * 1.1 MB per 65,536-header chunk of the pipelined paths; and the certificate
+ * directory, 157 bytes per certificate for as many as the largest batch had
+ * headers, 65,536 at the most (10 MB).
  *
  * Shared VRF key tables (deployment knob OURO_VRFKEY_SHARE, default 1): a
  * pool's VRF key is the same 32 bytes in every header it forges.  The same
@@ -247,8 +250,9 @@ int ouro_sum6kes_verify_batch(size_t n, const uint8_t *vk /* n x 32 */,
  * of -Y for it, and compute both U = [s]B - [c]Y of every header from that
  * table by additions alone.  U is a group element determined by (Y, c, s) and
  * its encoding is canonical, so verdicts and outputs are bit for bit those of
- * the per-header chains.  The grouping and the tables are rebuilt inside
- * every call; nothing is cached between calls.  A batch with fewer than 16
+ * the per-header chains.  A key's table is built by the first call on a
+ * stream that carries the key and kept for that stream's next calls
+ * (OURO_KEY_CACHE, below).  A batch with fewer than 16
  * headers per distinct key, or with more distinct keys than the table budget
  * holds, runs the per-header chains as before.  OURO_VRFKEY_SHARE=0 turns the
  * sharing off.  The latency plans, the host path and the standalone VRF entry
@@ -259,7 +263,22 @@ int ouro_sum6kes_verify_batch(size_t n, const uint8_t *vk /* n x 32 */,
  * min(n / 16, budget) keys -- at most OURO_VRFKEY_TAB_MB megabytes (default
  * 512: 5,900 keys; a 65,536-header chunk of the pipelined paths sizes for
  * 4,096 keys, 372 MB per slot in flight).  Lower the budget to trade memory
- * for speed; a batch whose keys do not fit loses nothing but the saving. */
+ * for speed; a batch whose keys do not fit loses nothing but the saving.  The
+ * tables' directory adds under 60 bytes per key.
+ *
+ * Kept between calls (deployment knob OURO_KEY_CACHE, default 1): a pool's VRF
+ * key lasts for the life of the pool and its certificate for months, so the
+ * two workspaces above keep, per stream, a directory of the keys seen: VRF key
+ * -> table and flag, certificate record -> verdict.  A call looks its headers
+ * up first -- the full key bytes are compared, a hash only picks where to look
+ * -- and builds or verifies only what is new.  Whether a call shares is still
+ * decided by the distinct keys of its own batch.  Nothing is shared between
+ * streams, threads or devices, and every access is ordered by the stream.  A
+ * directory is emptied when its workspace has to grow, when
+ * ouro_debug_reload_knobs() is called, and -- inside the call, with the same
+ * results -- when a batch's new keys do not fit beside the ones it holds.
+ * OURO_KEY_CACHE=0 empties both at every call: the behaviour before there was
+ * anything kept, for an A/B in one process. */
 typedef struct ouro_tpraos_batch {
   size_t n;
   const uint8_t *issuer_vk;        /* n x 32  bheaderVk (cold key)            */

@@ -22,11 +22,12 @@ int ouro_debug_host_path(unsigned long long *single_items,
                          unsigned long long *recomputed_batches);
 
 /* Re-read the library's environment switches (OURO_SINGLE_ITEM,
- * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_VRFKEY_*, OURO_BLOCK_SORT, OURO_HOST_*, OURO_CBOR_*,
+ * OURO_ON_DEVICE_ERROR, OURO_WIDE_SMALL_MAX, OURO_OCERT_SHARE, OURO_VRFKEY_*, OURO_KEY_CACHE, OURO_BLOCK_SORT, OURO_HOST_*, OURO_CBOR_*,
  * OURO_LAT_*, OURO_PLAN_*; csrc/knobs.h).  The library reads them once, on
  * first use, and never on a call path: a process that changes one (tests,
  * bench.py A/B passes) calls this afterwards.  Plans keep the values they
- * were created with. */
+ * were created with; the key directories kept between header launches
+ * (OURO_KEY_CACHE) are emptied. */
 void ouro_debug_reload_knobs(void);
 
 /* TIMING PROBE (bench.py latency phases) of the plan's last waited-for
@@ -94,6 +95,23 @@ int ouro_debug_last_ocert_groups(void *stream);
  * key).  Synchronises the stream: for tests only.  Negative: an OURO_E*
  * status. */
 int ouro_debug_last_vrfkey_groups(void *stream, int *shared);
+
+/* The key directories the calling thread's header launches on `stream` keep
+ * from launch to launch (OURO_KEY_CACHE in ouro_verify.h): out[0..2] = VRF
+ * keys resident, keys whose tables the last launch built, times the directory
+ * was emptied because new keys did not fit; out[3..5] = the same three for
+ * operational certificates (verified by the last launch); out[6] = the
+ * generation, one per launch; out[7] = 0.  The counts run on under
+ * OURO_KEY_CACHE=0 and start again from zero whenever a directory is laid out
+ * anew: its workspace grew, the knobs were reloaded, or a launch on the stream
+ * returned an error.  Zeros before the first launch and after a knob reload
+ * (which empties the directories).  With
+ * OURO_DEBUG_ALL_STREAMS for `stream`: the sums over every stream the thread
+ * has launched headers on -- the host-buffer entries' internal streams among
+ * them -- and the largest generation.  Synchronises the stream(s): for tests
+ * and tools only.  Returns OURO_OK or an OURO_E* status. */
+#define OURO_DEBUG_ALL_STREAMS ((void *)(intptr_t)-1)
+int ouro_debug_key_cache(void *stream, uint64_t out[8]);
 
 /* The calling thread's last raw-CBOR call (ouro_tpraos_verify_cbor /
  * ouro_integrity_verify_cbor): out6 = {total ms, ms gathering header bytes

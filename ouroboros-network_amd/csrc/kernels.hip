@@ -35,6 +35,8 @@
 #include "task_pool.h"
 #include "tpraos.h"
 #include "vrfkey_ws.h"
+#define OURO_KC_FN OURO_FI  // the directory's routines run in the kernels here
+#include "key_cache.h"
 #include "launches.h"
 #include "runtime.h"
 
@@ -166,17 +168,22 @@ __device__ unsigned long long g_clock_stamps[kClockSlots][4];
 // ---- one OCERT verification per distinct certificate (OURO_OCERT_SHARE) -----
 // An operational certificate is issued once per KES key rotation, so the
 // headers of a batch carry a handful of distinct ones per pool, and Ed25519
-// verification is a pure function of (key, message, signature).  Per call
-// (nothing is kept between calls):
-//   k_ocert_group   header i -> rep[i], the first header seen with the same
-//                   144 key bytes (tpraos.h ocert_key_*); the representatives
-//                   listed in uniq[0 .. *ctr);
+// verification is a pure function of (key, message, signature).  The verdicts
+// are kept from launch to launch in the stream's certificate directory
+// (key_cache.h, OURO_KEY_CACHE; the passes are listed at k_kc_begin).  Per
+// call:
+//   k_ocert_find    header i -> rep[i]: itself, with ocert_ok[i] copied from
+//                   the directory, when its 144 key bytes (tpraos.h
+//                   ocert_key_*) are found there; otherwise the first header
+//                   of the batch seen with the same bytes, those
+//                   representatives listed in uniq[0 .. fresh);
 //   k_ocert_unique_wide / k_ocert_unique   ocert_ok[uniq[k]] = the check, one
-//                   wave (small counts) or one lane per certificate;
+//                   wave (small counts) or one lane per NEW certificate;
+//   k_ocert_insert  the new certificates and their verdicts into the directory;
 //   k_tpraos_verify takes ocert_ok[rep[i]] as header i's OCERT flag and runs
 //                   the other five cores.
-// The count stays on the device (no synchronisation, capturable): every
-// kernel reads it and picks its form.  Above kOcertShareMax(n) distinct
+// The counts stay on the device (no synchronisation, capturable): every
+// kernel reads them and picks its form.  Above kOcertShareMax(n) distinct
 // certificates there is too little to share: the unique kernels return at
 // once and the header kernel runs the OCERT core inline as without sharing,
 // so a batch of distinct certificates costs the group pass and no more.  The
@@ -195,89 +202,185 @@ __host__ __device__ constexpr size_t kOcertShareMax(size_t n) {
 // degrades to the unshared cost, never to a wrong verdict or an unbounded loop)
 constexpr int kOcertProbeCap = 64;
 
-// table: cap_mask + 1 entries, zeroed by the launch (0 = empty, else header
-// index + 1).  Only the CAS's return value is used, never a plain load of the
-// table; the keys compared were written before the launch, so no fence is
-// needed.  hash_mask: all ones (the test build's OURO_TEST_OCERT_HASH_BITS
-// narrows it to exercise probe chains and the cap).
+// ---- the key directories' passes (key_cache.h, OURO_KEY_CACHE) ---------------
+// A pool's VRF key lasts for the life of the pool and its certificate for
+// months, so what a launch works out per distinct key is kept in the stream's
+// workspace and found again by the next launch on that stream.  Each of the
+// two instances (certificates, VRF keys) runs, stream-ordered:
+//   k_kc_begin     the next generation, the call's counts cleared; the per-call
+//                  grouping table cleared only if the call before left
+//                  entries in it (a warm step has none);
+//   k_*_find       the lookup, read-only on the directory, and the per-call
+//                  grouping of its misses (find_pass);
+//   k_kc_decide    the batch's distinct count = found + new, the sharing
+//                  decision from it as before, and whether the new keys fit;
+//   k_kc_reset     (they do not fit) empties the directory; for the VRF keys
+//                  k_vrfkey_find then runs again over the whole batch and
+//                  k_kc_decide once more;
+//   k_*_insert     one lane per new key: a slot, the key bytes, a cell;
+//   the build kernels over the new keys' list only.
+// The passes that have nothing to do return at once: their grids are sized on
+// the host, the counts stay on the device.  No lane waits for another lane's
+// write in any of them: probe, compare-and-swap, store.
+__global__ void __launch_bounds__(kBlock) k_kc_begin(uint32_t* hdr, uint4* table, size_t quads,
+                                                     uint32_t empty) {
+  // (the flag is written by k_kc_decide only)
+  const bool dirty = hdr[kKcDirty] != 0u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) kc_begin(hdr, empty != 0u);
+  if (!dirty) return;
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += nth)
+    table[q] = make_uint4(0u, 0u, 0u, 0u);
+}
+__global__ void k_kc_decide(uint32_t* hdr, uint32_t share_max, uint32_t slots, uint32_t readd,
+                            uint32_t after_reset) {
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    kc_decide(hdr, share_max, slots, readd != 0u, after_reset != 0u);
+}
+// table / quads: the per-call grouping table, cleared too when the grouping
+// runs again (regroup)
+__global__ void __launch_bounds__(kBlock) k_kc_reset(KcDir d, uint4* table, size_t quads,
+                                                     uint32_t regroup) {
+  // (k_kc_decide's flag; kc_reset_counts leaves it alone)
+  if (!d.hdr[kKcReset]) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) kc_reset_counts(d.hdr, regroup != 0u);
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint4* cells = reinterpret_cast<uint4*>(d.cells);
+  for (size_t q = tid; q < ((size_t)d.mask + 1) / 4; q += nth) cells[q] = make_uint4(0u, 0u, 0u, 0u);
+  if (regroup)
+    for (size_t q = tid; q < quads; q += nth) table[q] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// Header i against the directory, then (a miss) against the batch's own
+// headers.  table: cap_mask + 1 entries, all zero when the pass starts
+// (0 = empty, else header index + 1).  Only the CAS's return value is used,
+// never a plain load of the table; the keys compared were written before the
+// launch, and the directory is only read here, so no fence is needed.
+// hash_mask: all ones (the test build's OURO_TEST_OCERT_HASH_BITS narrows it
+// to exercise probe chains and the cap).  idx / ok (either may be null): a
+// found key's slot and its directory byte for header i.  retry: the pass
+// after k_kc_reset, which returns at once unless the directory was emptied;
+// nothing can be found then, so every header is grouped.
 template <class Key>
-__device__ __forceinline__ void group_pass(const ouro_tpraos_batch& b, uint32_t* table,
-                                           uint32_t cap_mask, uint32_t hash_mask,
-                                           uint32_t* __restrict__ rep,
-                                           uint32_t* __restrict__ uniq, uint32_t* ctr) {
+__device__ __forceinline__ void find_pass(const ouro_tpraos_batch& b, const KcDir& d,
+                                          uint32_t* table, uint32_t cap_mask, uint32_t hash_mask,
+                                          uint32_t* __restrict__ rep,
+                                          uint32_t* __restrict__ uniq,
+                                          uint32_t* __restrict__ idx, uint8_t* __restrict__ ok,
+                                          bool retry) {
+  if (retry && !d.hdr[kKcReset]) return;
+  const uint32_t gen = d.hdr[kKcGen];
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nth = (size_t)gridDim.x * blockDim.x;
   const uint32_t lid = threadIdx.x & 63u;
   for (size_t base = tid - lid; base < b.n; base += nth) {  // wave-uniform
     const size_t i = base + lid;
-    bool is_rep = false;
+    bool is_rep = false, first_hit = false;
     if (i < b.n) {
       uint32_t key[Key::kWords];
       Key::load(key, b, i);
       const uint64_t h = Key::hash(key);
-      uint32_t slot = (uint32_t)(h ^ (h >> 32)) & hash_mask & cap_mask;
-      uint32_t r = (uint32_t)i;
-      is_rep = true;  // also when the probe cap is reached
-      for (int probe = 0; probe < kOcertProbeCap; probe++) {
-        const uint32_t prev = atomicCAS(&table[slot], 0u, (uint32_t)i + 1u);
-        if (prev == 0u) break;
-        uint32_t other[Key::kWords];
-        Key::load(other, b, prev - 1u);
-        if (Key::equal(key, other)) {
-          r = prev - 1u;
-          is_rep = false;
-          break;
+      const int32_t found = retry ? -1 : kc_lookup<Key::kWords>(d, key, h, hash_mask);
+      if (found >= 0) {
+        rep[i] = (uint32_t)i;
+        if (idx) idx[i] = (uint32_t)found;
+        if (ok) ok[i] = d.val[found];
+        first_hit = kc_stamp(d, (uint32_t)found, gen);
+      } else {
+        uint32_t slot = kc_start(h, hash_mask, cap_mask);
+        uint32_t r = (uint32_t)i;
+        is_rep = true;  // also when the probe cap is reached
+        for (int probe = 0; probe < kOcertProbeCap; probe++) {
+          const uint32_t prev = atomicCAS(&table[slot], 0u, (uint32_t)i + 1u);
+          if (prev == 0u) break;
+          uint32_t other[Key::kWords];
+          Key::load(other, b, prev - 1u);
+          if (Key::equal(key, other)) {
+            r = prev - 1u;
+            is_rep = false;
+            break;
+          }
+          slot = (slot + 1u) & cap_mask;
         }
-        slot = (slot + 1u) & cap_mask;
+        rep[i] = r;
       }
-      rep[i] = r;
     }
-    // one add per wave of its representatives' count
+    // one add per wave of its representatives' count, one of its first stamps'
     const unsigned long long m = __ballot(is_rep);
     if (m) {
       uint32_t at = 0;
-      if (lid == (uint32_t)__ffsll((long long)m) - 1u) at = atomicAdd(ctr, (uint32_t)__popcll(m));
+      if (lid == (uint32_t)__ffsll((long long)m) - 1u)
+        at = atomicAdd(&d.hdr[kKcFresh], (uint32_t)__popcll(m));
       at = __shfl(at, __ffsll((long long)m) - 1);
       if (is_rep) uniq[at + __popcll(m & ((1ull << lid) - 1ull))] = (uint32_t)i;
     }
+    const unsigned long long mh = __ballot(first_hit);
+    if (mh && lid == (uint32_t)__ffsll((long long)mh) - 1u)
+      atomicAdd(&d.hdr[kKcHit], (uint32_t)__popcll(mh));
   }
 }
 // (the key loaders: tpraos.h OcertKey, the 144 certificate bytes, and VrfKey,
 // the 32 bytes of vrf_vk)
-__global__ void __launch_bounds__(kBlock) k_ocert_group(ouro_tpraos_batch b, uint32_t* table,
-                                                        uint32_t cap_mask, uint32_t hash_mask,
+__global__ void __launch_bounds__(kBlock) k_ocert_find(ouro_tpraos_batch b, KcDir d,
+                                                       uint32_t* table, uint32_t cap_mask,
+                                                       uint32_t hash_mask,
+                                                       uint32_t* __restrict__ rep,
+                                                       uint32_t* __restrict__ uniq,
+                                                       uint8_t* __restrict__ ocert_ok) {
+  find_pass<OcertKey>(b, d, table, cap_mask, hash_mask, rep, uniq, nullptr, ocert_ok, false);
+}
+__global__ void __launch_bounds__(kBlock) k_vrfkey_find(ouro_tpraos_batch b, KcDir d,
+                                                        uint32_t* table, uint32_t cap_mask,
+                                                        uint32_t hash_mask,
                                                         uint32_t* __restrict__ rep,
                                                         uint32_t* __restrict__ uniq,
-                                                        uint32_t* ctr) {
-  group_pass<OcertKey>(b, table, cap_mask, hash_mask, rep, uniq, ctr);
+                                                        uint32_t* __restrict__ kidx,
+                                                        uint32_t retry) {
+  find_pass<VrfKey>(b, d, table, cap_mask, hash_mask, rep, uniq, kidx, nullptr, retry != 0u);
 }
-__global__ void __launch_bounds__(kBlock) k_vrfkey_group(ouro_tpraos_batch b, uint32_t* table,
-                                                         uint32_t cap_mask, uint32_t hash_mask,
-                                                         uint32_t* __restrict__ rep,
-                                                         uint32_t* __restrict__ uniq,
-                                                         uint32_t* ctr) {
-  group_pass<VrfKey>(b, table, cap_mask, hash_mask, rep, uniq, ctr);
+// The new certificates of uniq[0 .. fresh) and the verdicts the unique pass
+// has just written, into the directory.  (A certificate that gets no slot or
+// no cell is verified again by the next launch that carries it.)
+__global__ void __launch_bounds__(kBlock) k_ocert_insert(ouro_tpraos_batch b, KcDir d,
+                                                         uint32_t hash_mask,
+                                                         const uint32_t* __restrict__ uniq,
+                                                         const uint8_t* __restrict__ ocert_ok) {
+  if (!d.hdr[kKcInsert]) return;
+  const uint32_t count = d.hdr[kKcWork], gen = d.hdr[kKcGen];
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += nth) {
+    const size_t i = uniq[k];
+    uint32_t key[OcertKey::kWords];
+    OcertKey::load(key, b, i);
+    const int32_t slot = kc_insert<OcertKey::kWords>(d, key, OcertKey::hash(key), hash_mask, gen);
+    if (slot >= 0) d.val[slot] = ocert_ok[i];
+  }
 }
 
 // ---- one fixed-base table of -Y per distinct VRF key (OURO_VRFKEY_SHARE) -----
-// A pool's VRF key is the same 32 bytes in every header it forges.  Per call
-// (nothing is kept between calls), after k_vrfkey_group has found the K
-// distinct keys (krep[i], kuniq[0 .. K)):
-//   k_vrfkey_base  key k on one lane: its flag (the checks of vrf_u_core), its
-//                  window base points (verify.h vrfkey_base) and
-//                  kidx[kuniq[k]] = k, so header i finds its table at
-//                  kidx[krep[i]];
-//   k_vrfkey_fill  (key, window) on one lane: the window's entries;
+// A pool's VRF key is the same 32 bytes in every header it forges.  A key's
+// table is built by the first launch on a stream that carries the key and
+// kept in its slot of the stream's key directory (key_cache.h) until the
+// directory is emptied: the workspace re-sized, the knobs reloaded, or new
+// keys that no longer fit.  Per call, after k_vrfkey_find has found the
+// batch's keys (krep[i]; kidx[i] = the slot of a key already there; the new
+// ones' representatives in kuniq[0 .. fresh)):
+//   k_vrfkey_insert  new key k on one lane: its slot s, kidx[kuniq[k]] = s and
+//                  nslot[k] = s, so header i finds its table at kidx[krep[i]];
+//   k_vrfkey_base  new key k on one lane: its flag (the checks of vrf_u_core)
+//                  and its window base points (verify.h vrfkey_base);
+//   k_vrfkey_fill  (new key, window) on one lane: the window's entries;
 //   k_tpraos_verify runs both U cores from the tables: additions only.
-// K stays on the device.  Above kmax keys (too few headers per key, or the
-// tables would not fit the budget: vrfkey_ws.h) the two build kernels return
-// at once and the header kernel runs the inline U cores, a wave-uniform
-// choice like the certificates'.
+// The counts stay on the device.  Above kmax distinct keys in THIS batch (too
+// few headers per key, or the tables would not fit the budget: vrfkey_ws.h)
+// nothing is inserted or built and the header kernel runs the inline U cores,
+// a wave-uniform choice like the certificates'.
 // (the header kernel takes one pointer to this record in device memory, null
 // when sharing is off; k_vrfkey_base writes it from its own arguments, so the
 // header kernel holds two registers for it, not twelve)
 struct VrfKeyShare {
-  const uint32_t* count = nullptr;  // K
+  const uint32_t* count = nullptr;  // the batch's distinct keys (the directory's kKcTotal)
   const uint32_t* krep = nullptr;
   const uint32_t* kidx = nullptr;
   const uint8_t* kflag = nullptr;
@@ -286,10 +389,29 @@ struct VrfKeyShare {
   uint32_t kmax = 0;
 };
 static_assert(sizeof(VrfKeyShare) <= 64, "the record's place in the grouping buffer (vrfkey_ws.h)");
+__global__ void __launch_bounds__(64) k_vrfkey_insert(ouro_tpraos_batch b, KcDir d,
+                                                      uint32_t hash_mask,
+                                                      const uint32_t* __restrict__ uniq,
+                                                      uint32_t* __restrict__ kidx,
+                                                      uint32_t* __restrict__ nslot) {
+  if (!d.hdr[kKcInsert]) return;
+  const uint32_t count = d.hdr[kKcWork], gen = d.hdr[kKcGen];
+  const size_t nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += nth) {
+    const size_t i = uniq[k];
+    uint32_t key[VrfKey::kWords];
+    VrfKey::load(key, b, i);
+    // (k_kc_decide lets this pass run only when every new key gets a slot)
+    const int32_t slot = kc_insert<VrfKey::kWords>(d, key, VrfKey::hash(key), hash_mask, gen);
+    kidx[i] = nslot[k] = slot >= 0 ? (uint32_t)slot : 0u;
+  }
+}
+// ctr: the new keys' count, or all ones when the launch does not share (the
+// directory's kKcWork)
 __global__ void __launch_bounds__(64) k_vrfkey_base(ouro_tpraos_batch b,
                                                     const uint32_t* __restrict__ ctr,
                                                     const uint32_t* __restrict__ uniq,
-                                                    uint32_t* __restrict__ kidx,
+                                                    const uint32_t* __restrict__ nslot,
                                                     uint8_t* __restrict__ kflag, int32_t* kbase,
                                                     uint32_t kmax, VrfKeyShare desc,
                                                     VrfKeyShare* out) {
@@ -298,14 +420,14 @@ __global__ void __launch_bounds__(64) k_vrfkey_base(ouro_tpraos_batch b,
   if (count > kmax) return;
   const size_t nth = (size_t)gridDim.x * blockDim.x;
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += nth) {
-    const size_t i = uniq[k];
+    const size_t i = uniq[k], s = nslot[k];
     uint32_t p[8];
     ld_words(p, b.vrf_vk + 32 * i, 2);
-    kflag[k] = vrfkey_base(p, kbase + k * kYBaseWords) ? 1 : 0;
-    kidx[i] = (uint32_t)k;
+    kflag[s] = vrfkey_base(p, kbase + s * kYBaseWords) ? 1 : 0;
   }
 }
 __global__ void __launch_bounds__(64) k_vrfkey_fill(const uint32_t* __restrict__ ctr,
+                                                    const uint32_t* __restrict__ nslot,
                                                     const int32_t* __restrict__ kbase,
                                                     int32_t* ktab, uint32_t kmax) {
   const uint32_t count = *ctr;
@@ -319,7 +441,8 @@ __global__ void __launch_bounds__(64) k_vrfkey_fill(const uint32_t* __restrict__
     const size_t k = blk * 64 + (r & 63);
     const int j = (int)(r >> 6);
     if (k >= count) continue;
-    vrfkey_fill(kbase + k * kYBaseWords, ktab + k * kYKeyWords, j);
+    const size_t s = nslot[k];
+    vrfkey_fill(kbase + s * kYBaseWords, ktab + s * kYKeyWords, j);
   }
 }
 
@@ -1085,6 +1208,92 @@ int launch_kes(hipStream_t st, size_t n, const uint8_t* vk, const uint32_t* t, c
 }
 
 
+// ---- a key directory's host side (key_cache.h, runtime.h KeyDirWs) ----
+// certificates a stream's directory holds at the most (157 B each)
+constexpr size_t kOcertDirSlots = 65536;
+struct KeyDir {
+  KcDir d;
+  uint32_t* extra = nullptr;  // a word per slot of the caller's (KcLayout off_extra)
+  bool empty = false;         // the host empties it for this launch: the cells ...
+  bool restart = false;       // ... and the counters too (generation, times emptied)
+  bool clear_tab = false;     // the host clears the per-call grouping table
+  // what the workspace records once the launch is enqueued whole (keydir_commit)
+  unsigned long long epoch = 0, tab_gen = 0, aux_gen = 0;
+  size_t tab_off = 0, tab_cap = 0;
+};
+// The directory of a launch that needs room for `slots` keys of `kw` words.
+// The workspace's record is taken down here (ws.valid) and put back by
+// keydir_commit after the launch's last kernel is enqueued: an error return
+// in between leaves a workspace that the next launch lays out and empties
+// from scratch, whatever its buffers hold by then.  The directory is laid out
+// anew and emptied, counters and all, when there is no valid record, when it
+// or the key tables (aux, null for the certificates) were allocated again,
+// when it has to grow, and when the knobs were reloaded.  OURO_KEY_CACHE=0
+// empties its cells at every launch and lets the counters run on.  The
+// per-call table (tab_cap entries at tab_off of tabbuf) is cleared from the
+// host unless the record says that the launch before left this very table,
+// in this very allocation, clear.
+static int keydir_prepare(KeyDirWs& ws, size_t slots, size_t kw, bool extra, const Buf& tabbuf,
+                          size_t tab_off, size_t tab_cap, KeyDir* out) {
+  const bool was_valid = ws.valid;
+  ws.valid = false;
+  const unsigned long long epoch = knob_epoch();
+  bool anew = !was_valid || slots > ws.slots || ws.epoch != epoch;
+  if (anew) ws.slots = slots;
+  const KcLayout L = kc_layout(ws.slots, kw, extra);
+  int rc = ensure(ws.dir, L.bytes);
+  if (rc) return rc;
+  anew = anew || ws.dir.gen != ws.dir_gen;
+  out->d = kc_dir(ws.dir.p, L, ws.slots);
+  out->extra = extra ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws.dir.p) + L.off_extra)
+                     : nullptr;
+  out->restart = anew;
+  out->empty = anew || !key_cache();
+  out->clear_tab = out->empty || tabbuf.gen != ws.tab_gen || tab_off != ws.tab_off ||
+                   tab_cap != ws.tab_cap;
+  out->epoch = epoch;
+  out->tab_gen = tabbuf.gen;
+  out->tab_off = tab_off;
+  out->tab_cap = tab_cap;
+  return OURO_OK;
+}
+// the slots' payload buffer (the VRF key tables), ensured after keydir_prepare:
+// allocated again, it holds no slot's table, so the directory starts over
+static void keydir_aux(const KeyDirWs& ws, const Buf& aux, KeyDir* kd) {
+  kd->aux_gen = aux.gen;
+  if (aux.gen != ws.aux_gen) kd->restart = kd->empty = kd->clear_tab = true;
+}
+// every kernel of the launch is enqueued: the next launch may rely on it
+static void keydir_commit(KeyDirWs& ws, const KeyDir& kd) {
+  ws.epoch = kd.epoch;
+  ws.dir_gen = ws.dir.gen;
+  ws.tab_gen = kd.tab_gen;
+  ws.aux_gen = kd.aux_gen;
+  ws.tab_off = kd.tab_off;
+  ws.tab_cap = kd.tab_cap;
+  ws.valid = true;
+}
+// grids of the passes that clear: a few workgroups per CU at the most
+static unsigned keydir_grid(size_t quads) {
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((quads + kBlock - 1) / kBlock, 1024));
+}
+static int keydir_begin(hipStream_t st, const KeyDir& kd, uint32_t* table, size_t cap) {
+  if (kd.restart)
+    OURO_HIP(hipMemsetAsync(kd.d.hdr, 0, 4 * ((size_t)kKcWords + kd.d.mask + 1), st));
+  else if (kd.empty)
+    OURO_HIP(hipMemsetAsync(kd.d.cells, 0, 4 * ((size_t)kd.d.mask + 1), st));
+  if (kd.clear_tab) OURO_HIP(hipMemsetAsync(table, 0, 4 * cap, st));
+  hipLaunchKernelGGL(k_kc_begin, dim3(keydir_grid(cap / 4)), dim3(kBlock), 0, st, kd.d.hdr,
+                     reinterpret_cast<uint4*>(table), cap / 4, kd.empty ? 1u : 0u);
+  return OURO_OK;
+}
+static void keydir_reset(hipStream_t st, const KeyDir& kd, uint32_t* table, size_t cap,
+                         bool regroup) {
+  const size_t quads = std::max<size_t>(((size_t)kd.d.mask + 1) / 4, regroup ? cap / 4 : 0);
+  hipLaunchKernelGGL(k_kc_reset, dim3(keydir_grid(quads)), dim3(kBlock), 0, st, kd.d,
+                     reinterpret_cast<uint4*>(table), cap / 4, regroup ? 1u : 0u);
+}
+
 // epochs (device memory, tpraos.h EpochTab block; null = none): the batch's
 // slots are looked up in it per header (kOptEpochs); the kernels find it where
 // the single eta0 would be
@@ -1131,50 +1340,64 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b_in, uint8_t* verdict, 
     ctx().vrfkey[st].last = nullptr;
     return OURO_OK;
   }
-  // One OCERT verification per distinct certificate (see k_ocert_group); the
-  // table's entries are header index + 1 and its capacity 2n in 32 bits.
+  // One OCERT verification per distinct certificate (see k_ocert_find); the
+  // per-call table's entries are header index + 1 and its capacity 2n in 32
+  // bits.  The directory holds as many certificates as the largest batch so
+  // far has headers, 65,536 at the most.
   OcertWs& ow = ctx().ocert[st];
   ow.last = nullptr;
   const uint32_t* rep = nullptr;
   const uint8_t* ocert_ok = nullptr;
   const uint32_t* count = nullptr;
+  const uint32_t hash_mask = ocert_hash_mask();
+  KeyDir okd, vkd;  // committed to their workspaces after the last kernel is enqueued
   if (ocert_share() && b.n >= 1 && b.n <= ((size_t)1 << 30)) {
     size_t cap = 64;
     while (cap < 2 * b.n) cap <<= 1;
-    // counter (one 16-B row) | table | rep | uniq | ocert_ok
-    const size_t bytes = 16 + 4 * cap + 4 * b.n + 4 * b.n + b.n;
+    // table | rep | uniq | ocert_ok
+    const size_t bytes = 4 * cap + 4 * b.n + 4 * b.n + b.n;
     if ((rc = ensure(ow.buf, bytes))) return rc;
-    uint32_t* ctr = static_cast<uint32_t*>(ow.buf.p);
-    uint32_t* table = ctr + 4;
+    uint32_t* table = static_cast<uint32_t*>(ow.buf.p);
     uint32_t* repw = table + cap;
     uint32_t* uniq = repw + b.n;
     uint8_t* okw = reinterpret_cast<uint8_t*>(uniq + b.n);
+    if ((rc = keydir_prepare(ow.kd, std::min(cap / 2, kOcertDirSlots), kOcertKeyWords, false,
+                             ow.buf, 0, cap, &okd)))
+      return rc;
     // the unique lane kernel in the header kernel's scratch slots: both plans
     // before either launch, the pointer taken after the buffer last grew
     int gu;
     if ((rc = plan(ds, kOcertUnique, b.n, st, &gu, &scr))) return rc;
     if ((rc = plan(ds, kHdr, b.n, st, &grid, &scr, kHdrLaneWords))) return rc;
-    OURO_HIP(hipMemsetAsync(ctr, 0, 16 + 4 * cap, st));
-    const size_t gg = (b.n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_ocert_group, dim3((unsigned)gg), dim3(kBlock), 0, st, b, table,
-                       (uint32_t)(cap - 1), ocert_hash_mask(), repw, uniq, ctr);
     const uint32_t wide_max = (uint32_t)std::min<size_t>(wide_small_max(), 0xffffffffu);
     const uint32_t share_max = (uint32_t)kOcertShareMax(b.n);
+    const KeyDir& kd = okd;
+    const uint32_t* work = kd.d.hdr + kKcWork;
+    if ((rc = keydir_begin(st, kd, table, cap))) return rc;
+    hipLaunchKernelGGL(k_ocert_find, dim3((unsigned)((b.n + kBlock - 1) / kBlock)), dim3(kBlock),
+                       0, st, b, kd.d, table, (uint32_t)(cap - 1), hash_mask, repw, uniq, okw);
+    hipLaunchKernelGGL(k_kc_decide, dim3(1), dim3(64), 0, st, kd.d.hdr, share_max, kd.d.slots, 0u,
+                       0u);
     if (wide_max)
       hipLaunchKernelGGL(k_ocert_unique_wide, dim3(wide_grid(std::min<size_t>(b.n, wide_max))),
-                         dim3(64), 0, st, b, ctr, uniq, okw, ds->btab, wide_max, share_max);
-    hipLaunchKernelGGL(k_ocert_unique, dim3(gu), dim3(kBlock), 0, st, b, ctr, uniq, okw, scr,
+                         dim3(64), 0, st, b, work, uniq, okw, ds->btab, wide_max, share_max);
+    hipLaunchKernelGGL(k_ocert_unique, dim3(gu), dim3(kBlock), 0, st, b, work, uniq, okw, scr,
                        ds->btab, wide_max, share_max);
+    keydir_reset(st, kd, table, cap, false);
+    hipLaunchKernelGGL(k_ocert_insert,
+                       dim3((unsigned)((std::min<size_t>(b.n, kd.d.slots) + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, st, b, kd.d, hash_mask, uniq, okw);
     rep = repw;
     ocert_ok = okw;
-    count = ctr;
-    ow.last = ctr;
+    count = kd.d.hdr + kKcTotal;
+    ow.last = count;
   } else if ((rc = plan(ds, kHdr, b.n, st, &grid, &scr, kHdrLaneWords))) {
     return rc;
   }
   // One fixed-base table of -Y per distinct VRF key (see k_vrfkey_base).  The
-  // tables are sized on the host for kmax keys (vrfkey_ws.h); the count stays
-  // on the device and the kernels compare it with kmax.
+  // tables and their directory are laid out on the host for the largest kmax
+  // so far (vrfkey_ws.h); the counts stay on the device and the kernels
+  // compare this batch's with this batch's kmax.
   VrfKeyWs& kw = ctx().vrfkey[st];
   kw.last = nullptr;
   const VrfKeyShare* ks = nullptr;
@@ -1182,26 +1405,43 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b_in, uint8_t* verdict, 
       vrfkey_share() ? vrfkey_layout(b.n, kYKeyBytes, vrfkey_tab_bytes()) : VrfKeyLayout{};
   if (L.kmax) {
     if ((rc = ensure(kw.group, L.group_bytes))) return rc;
-    if ((rc = ensure(kw.tables, L.table_bytes))) return rc;
     uint8_t* g = static_cast<uint8_t*>(kw.group.p);
-    uint32_t* ctr = reinterpret_cast<uint32_t*>(g);
     VrfKeyShare* desc = reinterpret_cast<VrfKeyShare*>(g + L.off_desc);
     uint32_t* table = reinterpret_cast<uint32_t*>(g + L.off_table);
     uint32_t* krep = reinterpret_cast<uint32_t*>(g + L.off_rep);
     uint32_t* kuniq = reinterpret_cast<uint32_t*>(g + L.off_uniq);
     uint32_t* kidx = reinterpret_cast<uint32_t*>(g + L.off_kidx);
-    uint8_t* kflag = g + L.off_flag;
-    // a key's table first (128-B entries on 128-B lines), the base points after
+    KeyDir& kd = vkd;
+    if ((rc = keydir_prepare(kw.kd, L.kmax, kVrfKeyWords, true, kw.group, L.off_table, L.cap, &kd)))
+      return rc;
+    // the slots' tables first (128-B entries on 128-B lines), their base points
+    // after; a directory laid out anew has just been emptied, so no table of
+    // the old allocation is looked for
+    const size_t slots = kd.d.slots;
+    if ((rc = ensure(kw.tables, slots * kYKeyBytes))) return rc;
+    keydir_aux(kw.kd, kw.tables, &kd);
     int32_t* ktab = static_cast<int32_t*>(kw.tables.p);
-    int32_t* kbase = ktab + L.kmax * kYKeyWords;
+    int32_t* kbase = ktab + slots * kYKeyWords;
+    uint8_t* kflag = kd.d.val;
+    uint32_t* nslot = kd.extra;
     const uint32_t kmax = (uint32_t)L.kmax;
-    OURO_HIP(hipMemsetAsync(ctr, 0, L.off_rep, st));
-    const size_t gg = (b.n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_vrfkey_group, dim3((unsigned)gg), dim3(kBlock), 0, st, b, table,
-                       (uint32_t)(L.cap - 1), ocert_hash_mask(), krep, kuniq, ctr);
+    const uint32_t* work = kd.d.hdr + kKcWork;
+    const unsigned gg = (unsigned)((b.n + kBlock - 1) / kBlock);
+    if ((rc = keydir_begin(st, kd, table, L.cap))) return rc;
+    hipLaunchKernelGGL(k_vrfkey_find, dim3(gg), dim3(kBlock), 0, st, b, kd.d, table,
+                       (uint32_t)(L.cap - 1), hash_mask, krep, kuniq, kidx, 0u);
+    hipLaunchKernelGGL(k_kc_decide, dim3(1), dim3(64), 0, st, kd.d.hdr, kmax, kd.d.slots, 1u, 0u);
+    // new keys that do not fit: the directory emptied and every key of the
+    // batch grouped and inserted again (three returns otherwise)
+    keydir_reset(st, kd, table, L.cap, true);
+    hipLaunchKernelGGL(k_vrfkey_find, dim3(gg), dim3(kBlock), 0, st, b, kd.d, table,
+                       (uint32_t)(L.cap - 1), hash_mask, krep, kuniq, kidx, 1u);
+    hipLaunchKernelGGL(k_kc_decide, dim3(1), dim3(64), 0, st, kd.d.hdr, kmax, kd.d.slots, 1u, 1u);
     // one wave per workgroup: the few lanes of a build spread over the CUs
+    hipLaunchKernelGGL(k_vrfkey_insert, dim3((unsigned)((L.kmax + 63) / 64)), dim3(64), 0, st, b,
+                       kd.d, hash_mask, kuniq, kidx, nslot);
     VrfKeyShare d;
-    d.count = ctr;
+    d.count = kd.d.hdr + kKcTotal;
     d.krep = krep;
     d.kidx = kidx;
     d.kflag = kflag;
@@ -1209,16 +1449,19 @@ int launch_hdr(hipStream_t st, const ouro_tpraos_batch& b_in, uint8_t* verdict, 
     d.ubtab = ds->ubtab;
     d.kmax = kmax;
     hipLaunchKernelGGL(k_vrfkey_base, dim3((unsigned)((L.kmax + 63) / 64)), dim3(64), 0, st, b,
-                       ctr, kuniq, kidx, kflag, kbase, kmax, d, desc);
+                       work, kuniq, nslot, kflag, kbase, kmax, d, desc);
     hipLaunchKernelGGL(k_vrfkey_fill, dim3((unsigned)((L.kmax + 63) / 64 * kYWindows)), dim3(64),
-                       0, st, ctr, kbase, ktab, kmax);
+                       0, st, work, nslot, kbase, ktab, kmax);
     ks = desc;
-    kw.last = ctr;
+    kw.last = d.count;
     kw.last_kmax = kmax;
   }
   hipLaunchKernelGGL(k_tpraos_verify, dim3(grid), dim3(kBlock), 0, st, b, verdict, be, bl, scr,
                      ds->btab, rep, ocert_ok, count, xopts, ks);
-  return launch_check();
+  if ((rc = launch_check())) return rc;
+  if (count) keydir_commit(ow.kd, okd);
+  if (ks) keydir_commit(kw.kd, vkd);
+  return OURO_OK;
 }
 
 int launch_leader(hipStream_t st, size_t n, const uint8_t* beta, const uint64_t* num,

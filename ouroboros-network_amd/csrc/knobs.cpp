@@ -11,6 +11,7 @@ namespace {
 Knobs g_knobs;
 std::once_flag g_once;
 std::mutex g_reload;
+std::atomic<unsigned long long> g_epoch{1};
 
 bool str_is(const char* name, const char* v) {
   const char* e = getenv(name);
@@ -40,6 +41,7 @@ void load(Knobs& k) {
   read_int(k.ocert_share, "OURO_OCERT_SHARE", 1);
   read_int(k.vrfkey_share, "OURO_VRFKEY_SHARE", 1);
   read_int<long long>(k.vrfkey_tab_mb, "OURO_VRFKEY_TAB_MB", 512);
+  read_int(k.key_cache, "OURO_KEY_CACHE", 1);
   read_size<size_t>(k.cbor_chunk, "OURO_CBOR_CHUNK", 0);
   read_size<size_t>(k.cbor_slots, "OURO_CBOR_SLOTS", 0);
   read_size<size_t>(k.cbor_copy_threads, "OURO_CBOR_COPY_THREADS", 0);
@@ -82,6 +84,9 @@ void reload() {
   std::call_once(g_once, [] {});
   std::lock_guard<std::mutex> lk(g_reload);
   load(g_knobs);
+  g_epoch.fetch_add(1, std::memory_order_relaxed);
 }
+
+unsigned long long epoch() { return g_epoch.load(std::memory_order_relaxed); }
 
 }  // namespace ouro_knobs

@@ -29,6 +29,7 @@ struct Knobs {
   std::atomic<int> ocert_share{1};           // OURO_OCERT_SHARE (0: every header's own OCERT check)
   std::atomic<int> vrfkey_share{1};          // OURO_VRFKEY_SHARE (0: every header's own U chains)
   std::atomic<long long> vrfkey_tab_mb{512}; // OURO_VRFKEY_TAB_MB (per-stream budget of the key tables)
+  std::atomic<int> key_cache{1};             // OURO_KEY_CACHE (0: every launch starts from empty key directories, A/B)
   // raw CBOR engine (0: the default; range-checked where used)
   std::atomic<size_t> cbor_chunk{0};         // OURO_CBOR_CHUNK
   std::atomic<size_t> cbor_slots{0};         // OURO_CBOR_SLOTS
@@ -62,5 +63,8 @@ struct Knobs {
 const Knobs& get();
 // re-read the environment (ouro_debug_reload_knobs)
 void reload();
+// the reloads so far: what is kept between calls under one set of knobs (the
+// key directories, key_cache.h) is dropped when this moves
+unsigned long long epoch();
 
 }  // namespace ouro_knobs

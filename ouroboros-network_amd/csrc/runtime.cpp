@@ -14,8 +14,10 @@
 #include <vector>
 
 #include "../../include/ouro_verify.h"
+#include "../../include/ouro_verify_debug.h"
 #include "hooks.h"
 #include "host_path.h"
+#include "key_cache.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launches.h"
@@ -157,6 +159,7 @@ int ensure(Buf& b, size_t bytes) {
   size_t want = std::max<size_t>(bytes, 4096);
   OURO_HIP(hipMalloc(&b.p, want));
   b.cap = want;
+  b.gen++;
   return OURO_OK;
 }
 
@@ -239,6 +242,14 @@ size_t vrfkey_tab_bytes() {
   const long long mb = ouro_knobs::get().vrfkey_tab_mb.load(std::memory_order_relaxed);
   return mb <= 0 ? 0 : (size_t)std::min<long long>(mb, 1ll << 20) << 20;
 }
+
+// The verdict of each distinct certificate and the table of each distinct VRF
+// key are kept per stream from one header launch to the next (key_cache.h;
+// kernels.hip k_kc_begin).  OURO_KEY_CACHE=0: every launch starts from empty
+// directories and works everything out again, for an A/B in one process.
+// knob_epoch: the directories are emptied when the knobs are reloaded.
+bool key_cache() { return ouro_knobs::get().key_cache.load(std::memory_order_relaxed) != 0; }
+unsigned long long knob_epoch() { return ouro_knobs::epoch(); }
 
 // The bits of the certificate hash the group pass uses.  The test-hook build
 // narrows them (OURO_TEST_OCERT_HASH_BITS=k) so that a few hundred headers
@@ -425,6 +436,45 @@ int ouro_debug_last_vrfkey_groups(void* stream, int* shared) {
   OURO_HIP(hipMemcpy(&count, it->second.last, sizeof count, hipMemcpyDeviceToHost));
   if (shared) *shared = count <= it->second.last_kmax ? 1 : 0;
   return (int)count;
+}
+
+// DIAGNOSTIC (tests, tools): the key directories of the calling thread on
+// `stream` (runtime.h KeyDirWs, key_cache.h): out = {VRF keys resident, built
+// by the last launch, times emptied; the same three for certificates; the
+// generation; 0}.  Zeros for a directory that does not exist yet.
+// OURO_DEBUG_ALL_STREAMS: the sums over every stream of the thread's context
+// (the host-buffer entries' own streams among them), the largest generation.
+// Synchronises the stream(s).
+int ouro_debug_key_cache(void* stream, uint64_t out[8]) {
+  if (!out) return fail(OURO_EINVAL, "null argument");
+  std::fill(out, out + 8, (uint64_t)0);
+  int dev;
+  int rc = current_device(&dev);
+  if (rc) return rc;
+  ThreadCtx& c = ctx_of(dev);
+  // (a directory a knob reload has overtaken is emptied by its next launch:
+  // it counts as empty here)
+  auto read = [&](hipStream_t st, const KeyDirWs& kd, uint64_t* o) -> int {
+    if (!kd.dir.p || !kd.slots || !kd.valid || kd.epoch != knob_epoch()) return OURO_OK;
+    OURO_HIP(hipStreamSynchronize(st));
+    uint32_t hdr[ouro::kKcWords];
+    OURO_HIP(hipMemcpy(hdr, kd.dir.p, sizeof hdr, hipMemcpyDeviceToHost));
+    o[0] += hdr[ouro::kKcResident];
+    o[1] += hdr[ouro::kKcBuilt];
+    o[2] += hdr[ouro::kKcEmptied];
+    out[6] = std::max<uint64_t>(out[6], hdr[ouro::kKcGen]);
+    return OURO_OK;
+  };
+  const bool all = stream == OURO_DEBUG_ALL_STREAMS;
+  for (auto& kv : c.vrfkey)
+    if ((all || kv.first == static_cast<hipStream_t>(stream)) &&
+        (rc = read(kv.first, kv.second.kd, out)))
+      return rc;
+  for (auto& ko : c.ocert)
+    if ((all || ko.first == static_cast<hipStream_t>(stream)) &&
+        (rc = read(ko.first, ko.second.kd, out + 3)))
+      return rc;
+  return OURO_OK;
 }
 
 // Contexts of the per-thread pool on `device` (runtime.h ThreadCtx):

@@ -61,6 +61,9 @@ int device_state(DeviceState** out);
 struct Buf {
   void* p = nullptr;
   size_t cap = 0;
+  // allocations so far (ensure): what was written into an earlier allocation
+  // is gone even when the new one comes back at the same address
+  unsigned long long gen = 0;
 };
 
 // The bytes a batch addresses by (offset, length) pairs: the window
@@ -154,24 +157,48 @@ struct RawPipe {
 // scratch keyed by that stream (work later enqueued on the same stream is
 // ordered after them).  Only the pool itself outlives the process (never
 // freed: the HIP runtime may be gone at teardown).
-// The OCERT sharing workspace of one stream (kernels.hip launch_hdr): the
-// counter, the open-addressing table, rep[n], uniq[n] and ocert_ok[n] --
-// 4 (next power of two >= 2n) + 9n bytes, about 17 MB at 1M headers.
-// last: the device counter of the stream's last header launch (null when that
-// launch did not share), for ouro_debug_last_ocert_groups.
+// What a sharing workspace keeps from launch to launch (key_cache.h): the
+// directory's buffer and the slots it is laid out for.  The rest is what the
+// last header launch that was enqueued WHOLE left behind, and what the next
+// one may rely on instead of clearing again: `valid` is taken down when a
+// launch starts and put back only when all of it is enqueued, so a launch
+// that returns an error half-way leaves a workspace the next launch empties.
+// epoch: the knob epoch (a reload empties the directory); dir_gen / tab_gen /
+// aux_gen: the allocations (Buf gen) of the directory, of the buffer the
+// per-call grouping table lies in and of the VRF tables; tab_off / tab_cap:
+// where in its buffer that table lay and its entries.  Allocations are told
+// apart by their count, never by their address.
+struct KeyDirWs {
+  Buf dir;
+  size_t slots = 0;
+  bool valid = false;
+  unsigned long long epoch = 0;
+  unsigned long long dir_gen = 0, tab_gen = 0, aux_gen = 0;
+  size_t tab_off = 0, tab_cap = 0;
+};
+
+// The OCERT sharing workspace of one stream (kernels.hip launch_hdr): per call
+// the open-addressing table, rep[n], uniq[n] and ocert_ok[n] -- 4 (next power
+// of two >= 2n) + 9n bytes, about 17 MB at 1M headers -- and, kept between
+// calls, the certificate directory (kd: up to 65,536 certificates at 157 B
+// each, 10 MB).  last: the device count of the stream's last header launch
+// (null when that launch did not share), for ouro_debug_last_ocert_groups.
 struct OcertWs {
   Buf buf;
+  KeyDirWs kd;
   const uint32_t* last = nullptr;
 };
 
 // The VRF key sharing workspace of one stream (kernels.hip launch_hdr,
-// vrfkey_ws.h): the grouping buffer (80 + 4 (next power of two >= 2n) + 12n
-// bytes and a flag per key) and the tables of up to kmax keys (verify.h kYKeyBytes
-// each, at most OURO_VRFKEY_TAB_MB in all).  last / last_kmax: the device
-// count of the stream's last header launch and the kmax it ran with (null
-// when that launch built no tables), for ouro_debug_last_vrfkey_groups.
+// vrfkey_ws.h): per call the grouping buffer (80 + 4 (next power of two >= 2n)
+// + 12n bytes); kept between calls the tables of up to kd.slots keys (verify.h
+// kYKeyBytes each, at most OURO_VRFKEY_TAB_MB in all) and their directory (kd,
+// under 60 B per slot).  last / last_kmax: the device count of the stream's last
+// header launch and the kmax it ran with (null when that launch did no
+// grouping), for ouro_debug_last_vrfkey_groups.
 struct VrfKeyWs {
   Buf group, tables;
+  KeyDirWs kd;
   const uint32_t* last = nullptr;
   uint32_t last_kmax = 0;
 };
@@ -225,6 +252,8 @@ bool ocert_share();
 uint32_t ocert_hash_mask();
 bool vrfkey_share();
 size_t vrfkey_tab_bytes();
+bool key_cache();
+unsigned long long knob_epoch();
 int lat_block();
 int lat_quad();
 int lat_wide_mask();

@@ -25,6 +25,9 @@ constexpr size_t kVrfKeyMinPerKey = OURO_VRFKEY_MIN_PER_KEY;
 //   counter (one 16-B row) | the header kernel's record (64 B) | table[cap] |
 //   rep[n] | uniq[n] | kidx[n] | flag[kmax]
 // table entries are header index + 1 in 32 bits, cap the power of two >= 2n.
+// (The counts and the keys' flags now live in the stream's key directory,
+// key_cache.h, which outlives the call; their places here stay, unused, so
+// that the offsets are the ones the layout check pins.)
 struct VrfKeyLayout {
   size_t kmax = 0;       // distinct keys the tables are sized for (0: do not share)
   size_t cap = 0;        // entries of the open-addressing table
