@@ -15,6 +15,7 @@
 #include "leader.h"
 #include "ledger_view.h"
 #include "tpraos.h"
+#include "wide_cores.h"
 
 using namespace ouro;
 
@@ -503,6 +504,49 @@ int dh_lt_v(int n, int stride, const uint32_t* in, uint32_t* out) {
     Lane lane;
     lt::v_item(in + (size_t)i * lt::kVIn, out + (size_t)i * lt::kChainOut, lane.s, host_btab());
   }
+  return 0;
+}
+
+// ---- the latency mode's split helpers and wide B table (wide_cores.h, verify.h)
+// the signed width-4 digits of s as pw_dsm forms them (sc_recode_carries<4, 64>,
+// sc_digit_from<4>), and the carry mask
+unsigned long long dh_wide_recode4(const uint32_t s[8], int32_t digits[64]) {
+  const uint64_t c = sc_recode_carries<4, 64>(s);
+  for (int j = 0; j < 64; j++)
+    digits[j] = sc_digit_from<4>((s[j >> 3] >> (4 * (j & 7))) & 15u, c, j, 64);
+  return c;
+}
+void dh_wide_high_half(uint32_t hh[8], const uint32_t h[8]) { wide::sc_high_half_with_carry(hh, h); }
+// the cuts the host build instantiates: the product's V / V2 window, the V2 /
+// V3 one relative to it (used with OURO_LAT_V3), and one more each with 4 K a
+// multiple of 32 and not
+#define DH_WIDE_KS OURO_LAT_VWIN, (OURO_LAT_VWIN2 - OURO_LAT_VWIN) & 63, 16, 29
+int dh_wide_split_ks(int ks[4], int* v3) {
+  const int k[4] = {DH_WIDE_KS};
+  for (int i = 0; i < 4; i++) ks[i] = k[i];
+  *v3 = OURO_LAT_V3;
+  return 4;
+}
+int dh_wide_high_from_window(int which, uint32_t hh[8], const uint32_t s[8]) {
+  constexpr int k[4] = {DH_WIDE_KS};
+  switch (which) {
+    case 0: wide::sc_high_from_window<k[0]>(hh, s); return k[0];
+    case 1: wide::sc_high_from_window<k[1]>(hh, s); return k[1];
+    case 2: wide::sc_high_from_window<k[2]>(hh, s); return k[2];
+    case 3: wide::sc_high_from_window<k[3]>(hh, s); return k[3];
+  }
+  return -1;
+}
+// entry idx (= k - 1) of half `half` of the wide B table, built as runtime.cpp
+// builds it (build_btab_wide over the niels tables), once per process
+int dh_btab_wide_entry(int half, int idx, uint16_t out[kBWideU16]) {
+  if (half < 0 || half > 1 || idx < 0 || idx >= kBTabEntries) return -1;
+  static const std::vector<uint16_t> tab = [] {
+    std::vector<uint16_t> t(2 * kBTabWideWords);
+    build_btab_wide(t.data(), host_btab());
+    return t;
+  }();
+  memcpy(out, tab.data() + ((size_t)half * kBTabEntries + idx) * kBWideU16, sizeof(uint16_t) * kBWideU16);
   return 0;
 }
 }

@@ -25,13 +25,19 @@
 //   v_permlane32_swap (gfx950) so every row holds all four again.
 //
 // Limb bounds (signed): a carried element has |limb| <= 65,535 + 38*16 <
-// 2^16.01.  The rotated operand g of a product passes through v_mul_i32_i24
-// (x38 at lane 0, x1 elsewhere) after it wrapped, so |38 g| < 2^23, i.e. |g|
-// <= 3 carried elements summed (<= 196,833 < 220,752); the broadcast operand
-// f is a full 32-bit input of v_mad_i64_i32 and takes the 4-term sums.  The
-// accumulator is then below 16 * 2^18.01 * 2^23 < 2^45.1, so its >> 16 fits
-// an int32, and the carry rounds stay inside the i24 ranges they use.  Every
-// formula below puts its narrow (<= 3-term) operand second.
+// 2^16.01 after fw_carry's three rounds, < 2^16.03 after fw_carry2 and <
+// 2^16.13 (71,716) after fw_carry_rows; limb 15, whose carry-in is never
+// multiplied by 38, stays within [-16, 65,550] in every form.  The rotated
+// operand g of a product passes through v_mul_i32_i24 (x38 at lane 0, x1
+// elsewhere) after it wrapped, so |38 g| < 2^23, i.e. |g| <= 220,752: 3
+// carried elements summed (<= 215,148); the broadcast operand f is a full
+// 32-bit input of v_mad_i64_i32 and takes the 4-term sums (<= 286,864).  The
+// accumulator is then below 571 * 286,864 * 220,752 < 2^45.1, so its >> 16
+// fits an int32, and the carry rounds stay inside the i24 ranges they use.
+// Every formula below puts its narrow (<= 3-term) operand second.
+// tests/wide_vectors.py restates this arithmetic on exact integers and holds
+// each of these numbers to it; tests/test_wide_exact.py runs every routine
+// here on the device with limbs at these bounds.
 //
 // Device-only: every routine here is wave-collective (DPP, permlane).
 #pragma once
@@ -157,7 +163,8 @@ __device__ __forceinline__ int64_t add_rows_u64(int64_t a) {
   return (int64_t)(((uint64_t)h2[0] << 32 | l2[0]) + ((uint64_t)h2[1] << 32 | l2[1]));
 }
 // The replicated products' carry: each row's partial accumulator (four
-// steps: |acc_r| < 2^43.1) goes through the first carry round by itself
+// steps: |acc_r| <= 4 * 286,864 * 38 * 220,752 < 2^43.2 with a 4-term
+// broadcast operand) goes through the first carry round by itself
 // (a0 + a1 + a2 of fw_carry2, below 2^21.4), the four rows' 32-bit results
 // are summed across rows (below 2^23.4), then the last shift-and-rotate
 // round: limbs below 2^16 + 38 * 2^7.4 < 2^16.13 (3 of them sum below
@@ -236,7 +243,13 @@ __device__ __forceinline__ int32_t fe_to_fw(const fe& f, const Lanes& L) {
 // fw -> lane-local fe in every lane (limbs within fe's reduced profile,
 // limb 0 up to 2^26 + 18): row `row`'s limbs read out with v_readlane
 __device__ __forceinline__ fe fw_to_fe(int32_t x, int row = 0) {
-  // + 4p first (limbs 4 * (0xffed, 0xffff x 14, 0x7fff) >= 2^17 > |negative limb|)
+  // + 4p first (limbs 4 * (0xffed, 0xffff x 14, 0x7fff)): limb k may be as
+  // negative as 4 p_k -- 262,068 at limbs 0..14 but only 131,068 at limb 15
+  // (below 2^17: limbs 14 and 15 at -(2^17 - 1) would leave a negative final
+  // carry, which the fold below takes only while 38 |c| does not borrow out
+  // of limb 0).  The callers pass two-term
+  // differences of carried elements at most: limbs 0..14 above -2 * 71,716,
+  // limb 15 above -65,566.
   uint32_t h[16];
   int32_t c = 0;
 #pragma unroll

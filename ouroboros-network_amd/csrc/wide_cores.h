@@ -5,6 +5,10 @@
 // encoding checks, lane-local decode algebra) runs on every lane alike; lane
 // 0 stores the header record's fields exactly as the lane routines do, so
 // the finish (k_tpraos_finish) is shared.
+// tests/test_wide_exact.py pins the pieces one by one against exact integers:
+// the decodes, fw_norm, pw_is_identity, the encodings, every pw_dsm
+// instantiation made here with its window counts, and the split forms' halves
+// (eds_chain, vrf_sh_split) summed; the split helpers also on the host build.
 #pragma once
 #include "tpraos.h"
 #include "wide.h"
@@ -20,6 +24,59 @@ constexpr int kStampItems = 16, kStampTags = 24;
 #if OURO_LAT_STAMPS
 __device__ unsigned long long g_lat_stamps[kStampItems][kStampTags];
 #endif
+namespace wide {
+// ---- the split forms' scalar helpers (host and device: tests/test_wide_exact.py
+// checks them against exact integers on the host build) ---------------------
+// h >> 128 plus the carry h's signed windows 0..31 hand to window 32
+OURO_FI void sc_high_half_with_carry(uint32_t hh[8], const uint32_t h[8]) {
+  const uint32_t cin = (uint32_t)(sc_recode_carries<4, 64>(h) >> 32) & 1u;
+  uint64_t c = cin;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    c += h[4 + i];
+    hh[i] = (uint32_t)c;
+    c >>= 32;
+    hh[4 + i] = 0;
+  }
+}
+
+// The windows at which the split form cuts s between its V items.  V2 pays
+// 4 K doublings to 2^(4K) H before its chain over windows K..63, so its time
+// is ~253 doublings plus the additions of its windows whatever K, while V's
+// chain grows with K: K = 32 (bit 128, rounds 3--4) left V2 32 additions
+// that V did not wait for; 48 ends the two chains together (profiles/r05d).
+// OURO_LAT_V3 = 1 cuts once more, at K2: V2 then takes windows K..K2-1 and a
+// V3 item (H again, 4 K2 doublings) windows K2..63, which takes all but a few
+// additions off the item that does the ~253 doublings.
+#ifndef OURO_LAT_VWIN
+#define OURO_LAT_VWIN (OURO_LAT_V3 ? 49 : 48)
+#endif
+#ifndef OURO_LAT_VWIN2
+#define OURO_LAT_VWIN2 61
+#endif
+static_assert(OURO_LAT_VWIN >= 8 && OURO_LAT_VWIN <= 60, "V / V2 split window");
+static_assert(!OURO_LAT_V3 || (OURO_LAT_VWIN2 > OURO_LAT_VWIN && OURO_LAT_VWIN2 <= 63),
+              "V2 / V3 split window");
+
+// (s >> 4K) plus the carry s's signed windows 0..K-1 hand to window K: the
+// windows below K recoded from the whole s plus [that]·16^K are s exactly
+// (pw_dsm recodes its scalar whole and adds only the windows it is given)
+template <int K>
+OURO_FI void sc_high_from_window(uint32_t hh[8], const uint32_t s[8]) {
+  const uint32_t cin = (uint32_t)(sc_recode_carries<4, 64>(s) >> K) & 1u;
+  constexpr int kW = (4 * K) >> 5, kB = (4 * K) & 31;
+  uint64_t c = cin;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint32_t w = i + kW < 8 ? s[i + kW] >> kB : 0u;
+    if (kB != 0 && i + kW + 1 < 8) w |= s[i + kW + 1] << ((32 - kB) & 31);
+    c += w;
+    hh[i] = (uint32_t)c;
+    c >>= 32;
+  }
+}
+}  // namespace wide
+
 #if defined(__HIP_DEVICE_COMPILE__)
 namespace wide {
 
@@ -912,19 +969,6 @@ __device__ __forceinline__ void eds_double(Slot e, const uint32_t pk[8]) {
   st_pw(e + kEsA128, P);
 }
 
-// h >> 128 plus the carry h's signed windows 0..31 hand to window 32
-OURO_FI void sc_high_half_with_carry(uint32_t hh[8], const uint32_t h[8]) {
-  const uint32_t cin = (uint32_t)(sc_recode_carries<4, 64>(h) >> 32) & 1u;
-  uint64_t c = cin;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    c += h[4 + i];
-    hh[i] = (uint32_t)c;
-    c >>= 32;
-    hh[4 + i] = 0;
-  }
-}
-
 __device__ __forceinline__ void eds_chain(Slot e, const uint16_t* bw, bool high) {
   const Lanes L = lanes();
   uint32_t h[8], S[8], a[8];
@@ -945,42 +989,6 @@ __device__ __forceinline__ bool eds_combine(Slot e) {
   const int32_t d2 = d2_wide(L);
   const pw Q = pw_add_p3(pw_add_p3(ld_pw(e + kEsX), ld_pw(e + kEsY), d2, L), ld_pw(e + kEsR), d2, L);
   return ldg1(e.word(kEsOk)) != 0 && pw_is_identity(Q);
-}
-
-// The windows at which the split form cuts s between its V items.  V2 pays
-// 4 K doublings to 2^(4K) H before its chain over windows K..63, so its time
-// is ~253 doublings plus the additions of its windows whatever K, while V's
-// chain grows with K: K = 32 (bit 128, rounds 3--4) left V2 32 additions
-// that V did not wait for; 48 ends the two chains together (profiles/r05d).
-// OURO_LAT_V3 = 1 cuts once more, at K2: V2 then takes windows K..K2-1 and a
-// V3 item (H again, 4 K2 doublings) windows K2..63, which takes all but a few
-// additions off the item that does the ~253 doublings.
-#ifndef OURO_LAT_VWIN
-#define OURO_LAT_VWIN (OURO_LAT_V3 ? 49 : 48)
-#endif
-#ifndef OURO_LAT_VWIN2
-#define OURO_LAT_VWIN2 61
-#endif
-static_assert(OURO_LAT_VWIN >= 8 && OURO_LAT_VWIN <= 60, "V / V2 split window");
-static_assert(!OURO_LAT_V3 || (OURO_LAT_VWIN2 > OURO_LAT_VWIN && OURO_LAT_VWIN2 <= 63),
-              "V2 / V3 split window");
-
-// (s >> 4K) plus the carry s's signed windows 0..K-1 hand to window K: the
-// windows below K recoded from the whole s plus [that]·16^K are s exactly
-// (pw_dsm recodes its scalar whole and adds only the windows it is given)
-template <int K>
-OURO_FI void sc_high_from_window(uint32_t hh[8], const uint32_t s[8]) {
-  const uint32_t cin = (uint32_t)(sc_recode_carries<4, 64>(s) >> K) & 1u;
-  constexpr int kW = (4 * K) >> 5, kB = (4 * K) & 31;
-  uint64_t c = cin;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    uint32_t w = i + kW < 8 ? s[i + kW] >> kB : 0u;
-    if (kB != 0 && i + kW + 1 < 8) w |= s[i + kW + 1] << ((32 - kB) & 31);
-    c += w;
-    hh[i] = (uint32_t)c;
-    c >>= 32;
-  }
 }
 
 // V = [s]H - [c]Gamma over THREE waves: [s windows 0..K-1]H (the V item,

@@ -1,12 +1,16 @@
 // wide_test.hip -- TEST-ONLY: the wave-wide arithmetic of wide.h checked
 // against the lane-local routines it replaces (fe25519.h / ge25519.h), on the
 // device, one wave per case.  tests/test_gpu_wide.py drives it; the product
-// library does not contain this file.
+// library does not contain this file.  The same routines one by one on host
+// records (ouro_wx_op), for the exact-integer comparison of
+// tests/test_wide_exact.py.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
+#include "launch.h"
 #include "verify.h"
+#include "wide_blake2b.h"
 #include "wide_cores.h"
 
 using namespace ouro;
@@ -379,9 +383,330 @@ __global__ void __launch_bounds__(64) k_wide_sha130_pairs(int pairs, const uint3
 #endif
 }
 
+// ---- the wave-wide routines one by one (tests/test_wide_exact.py) --------------
+// One wave per record.  A record is kWxIn slots of 64 int32 words in and
+// kWxOut slots out: word `lane` of a slot is that lane's own operand (raw
+// signed limbs, replicated or not as the host wrote them) or result, and the
+// wave-uniform inputs (scalars, byte strings, counts) sit in the first words
+// of a slot, read by every lane alike.  Every routine here is wave-collective:
+// no lane leaves early, and every lane stores its own word of every result.
+// The field items keep the other test kernels' bound of 64; the items that run
+// tables, chains and the split parts carry k_tpraos_cores' launch bounds
+// (kernels_lat.hip), so their register budget is the product's.
+#ifndef OURO_LAT_WAVES
+#define OURO_LAT_WAVES 2
+#endif
+constexpr int kWxIn = 10, kWxOut = 20;
+enum WxOp {
+  kWxMul, kWxSq, kWxMulRep, kWxSqRep, kWxCarry3, kWxCarry2, kWxCarryRows, kWxNorm, kWxGather,
+  kWxSel4, kWxAddRows32, kWxAddRows64, kWxFeToFw, kWxToFe, kWxPowRows, kWxPow, kWxInv, kWxInvSel,
+  kWxFieldOps,  // the items above: __launch_bounds__(64)
+  kWxDbl = kWxFieldOps, kWxAdd, kWxTab, kWxAddP3, kWxIsId, kWxStLd, kWxEnc, kWxDecode,
+  kWxDecodePair, kWxDsm, kWxDsmT2, kWxDsmB1, kWxDsmB2, kWxDsmB, kWxDsmT2B, kWxEdHalf, kWxVPart,
+  kWxBlake, kWxOps
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ int32_t wx_pick8(const uint32_t w[8], uint32_t k) {
+  uint32_t v = w[0];
+#pragma unroll
+  for (uint32_t i = 1; i < 8; i++) v = k == i ? w[i] : v;
+  return (int32_t)v;
+}
+// this lane's word (lane & 7) of the canonical value of f
+__device__ __forceinline__ int32_t wx_word(const fe& f) {
+  uint32_t w[8];
+  fe_to_words(w, f);
+  return wx_pick8(w, threadIdx.x & 7u);
+}
+
+template <int kOp>
+__device__ __forceinline__ void wx_item(const int32_t* rin, int32_t* rout, const uint16_t* bw) {
+  using namespace wide;
+  static_assert(kSlotGroup == 1, "st_pw / ld_pw into a record slot");
+  const Lanes L = lanes();
+  const uint32_t lane = threadIdx.x & 63u;
+  auto I = [&](int k) { return rin[64 * k + lane]; };              // this lane's word
+  auto U = [&](int k, int w) { return (uint32_t)rin[64 * k + w]; };  // wave-uniform word
+  auto O = [&](int k, int32_t v) { rout[64 * k + lane] = v; };
+  auto acc64 = [&](int k) { return (int64_t)(((uint64_t)(uint32_t)I(k + 1) << 32) | (uint32_t)I(k)); };
+  auto Opw = [&](int k, const pw& P) { O(k, P.X); O(k + 1, P.Y); O(k + 2, P.Z); O(k + 3, P.T); };
+  auto Ipw = [&](int k) { return pw{I(k), I(k + 1), I(k + 2), I(k + 3)}; };
+  auto Oenc = [&](int k, const uint32_t e[8]) { O(k, wx_pick8(e, lane & 7u)); };
+  auto words8 = [&](uint32_t w[8], int k, int at) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = U(k, at + i);
+  };
+  if constexpr (kOp == kWxMul) O(0, fw_mul(I(0), I(1), L));
+  if constexpr (kOp == kWxSq) O(0, fw_sq(I(0), L));
+  if constexpr (kOp == kWxMulRep) O(0, fw_mul_rep(I(0), I(1), L));
+  if constexpr (kOp == kWxSqRep) O(0, fw_sq_rep(I(0), L));
+  if constexpr (kOp == kWxCarry3) O(0, fw_carry(acc64(0), L.fac));
+  if constexpr (kOp == kWxCarry2) O(0, fw_carry2(acc64(0), L.fac, L.fac2));
+  if constexpr (kOp == kWxCarryRows) O(0, fw_carry_rows(acc64(0), L));
+  if constexpr (kOp == kWxNorm) O(0, fw_norm(I(0), L));
+  if constexpr (kOp == kWxGather) {
+    const fw4 g = fw_gather(I(0));
+    O(0, g.r0); O(1, g.r1); O(2, g.r2); O(3, g.r3);
+  }
+  if constexpr (kOp == kWxSel4) O(0, sel4(I(0), I(1), I(2), I(3), L));
+  if constexpr (kOp == kWxAddRows32) O(0, add_rows_i32(I(0)));
+  if constexpr (kOp == kWxAddRows64) {
+    const int64_t s = add_rows_u64(acc64(0));
+    O(0, (int32_t)(uint32_t)s);
+    O(1, (int32_t)(uint32_t)((uint64_t)s >> 32));
+  }
+  if constexpr (kOp == kWxFeToFw) {
+    uint32_t w[8];
+    words8(w, 0, 0);
+    O(0, fe_to_fw(fe_from_words(w), L));
+  }
+  if constexpr (kOp == kWxToFe) {  // slots 0..3: fw_to_fe(x, row); 4: own row; 5, 6: zero tests
+    const int32_t x = I(0);
+    O(0, wx_word(fw_to_fe(x, 0)));
+    O(1, wx_word(fw_to_fe(x, 1)));
+    O(2, wx_word(fw_to_fe(x, 2)));
+    O(3, wx_word(fw_to_fe(x, 3)));
+    const fe own = fw_to_fe_own_row(x);
+    O(4, wx_word(own));
+    O(5, (fw_row_iszero(x, 0) ? 1 : 0) | (fw_row_iszero(x, 1) ? 2 : 0) |
+             (fw_row_iszero(x, 2) ? 4 : 0) | (fw_row_iszero(x, 3) ? 8 : 0));
+    O(6, fe_iszero(own) ? 1 : 0);
+  }
+  if constexpr (kOp == kWxPowRows) O(0, fw_pow22523_rows(I(0)));
+  if constexpr (kOp == kWxPow) O(0, fw_pow22523(I(0)));
+  if constexpr (kOp == kWxInv) O(0, fw_invert(I(0)));
+  if constexpr (kOp == kWxInvSel) O(0, fw_invert_sel(I(0), L));
+  if constexpr (kOp == kWxDbl) Opw(0, pw_dbl(Ipw(0), L));
+  if constexpr (kOp == kWxAdd) {  // P + Q, P - Q, and Q's two cached operands
+    const pw P = Ipw(0);
+    const cw q = pw_cached(Ipw(4), d2_wide(L), L);
+    Opw(0, pw_add(P, q.pos, L));
+    Opw(4, pw_add(P, q.neg, L));
+    O(8, q.pos);
+    O(9, q.neg);
+  }
+  if constexpr (kOp == kWxTab) {  // slot d + 8: this row's operand of [d]P, d = -8..8
+    TabW t;
+    tab_build(t, Ipw(0), d2_wide(L), L);
+#pragma unroll 1
+    for (int d = -8; d <= 8; d++) O(d + 8, tab_pick(t, __builtin_amdgcn_readfirstlane(d)));
+  }
+  if constexpr (kOp == kWxAddP3) Opw(0, pw_add_p3(Ipw(0), Ipw(4), d2_wide(L), L));
+  if constexpr (kOp == kWxIsId) O(0, pw_is_identity(Ipw(0)) ? 1 : 0);
+  if constexpr (kOp == kWxStLd) {  // through record memory, as between two items
+    const Slot s{rout + 64 * 8};
+    st_pw(s, Ipw(0));
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+    Opw(0, ld_pw(s));
+  }
+  if constexpr (kOp == kWxEnc) {  // slots 0, 1: encode2_wide(H, V); 2, 3: encode1_wide of each
+    const pw H = Ipw(0), V = Ipw(4);
+    uint32_t eh[8], ev[8], e1[8], e2[8];
+    encode2_wide(eh, ev, H, V);
+    encode1_wide(e1, H);
+    encode1_wide(e2, V);
+    Oenc(0, eh); Oenc(1, ev); Oenc(2, e1); Oenc(3, e2);
+  }
+  if constexpr (kOp == kWxDecode) {  // slot 0: ok; 1..4: X, Y, Z, T canonical
+    uint32_t s[8];
+    words8(s, 0, 0);
+    ge_p3 P;
+    const bool ok = ge_decode_wide(&P, s, U(0, 8) != 0);
+    O(0, ok ? 1 : 0);
+    O(1, wx_word(P.X)); O(2, wx_word(P.Y)); O(3, wx_word(P.Z)); O(4, wx_word(P.T));
+  }
+  if constexpr (kOp == kWxDecodePair) {  // a: slots 0..4, b: slots 5..9
+    uint32_t sa[8], sb[8];
+    words8(sa, 0, 0);
+    words8(sb, 0, 8);
+    ge_p3 A, B;
+    bool oka, okb;
+    ge_decode_pair_wide(&A, &oka, &B, &okb, sa, sb, U(0, 16) != 0);
+    O(0, oka ? 1 : 0);
+    O(1, wx_word(A.X)); O(2, wx_word(A.Y)); O(3, wx_word(A.Z)); O(4, wx_word(A.T));
+    O(5, okb ? 1 : 0);
+    O(6, wx_word(B.X)); O(7, wx_word(B.Y)); O(8, wx_word(B.Z)); O(9, wx_word(B.T));
+  }
+  if constexpr (kOp >= kWxDsm && kOp <= kWxDsmT2B) {
+    // T1: slots 0..3, T2: 4..7; slot 8: a1, a2, b (8 words each), nw1, nw2
+    constexpr bool kT2 = kOp == kWxDsmT2 || kOp == kWxDsmT2B;
+    uint32_t a1[8], a2[8], b[8];
+    words8(a1, 8, 0);
+    words8(a2, 8, 8);
+    words8(b, 8, 16);
+    const int nw1 = (int)U(8, 24), nw2 = (int)U(8, 25);
+    const int32_t d2 = d2_wide(L);
+    TabW t1, t2;
+    tab_build(t1, Ipw(0), d2, L);
+    if constexpr (kT2) tab_build(t2, Ipw(4), d2, L);
+    pw R;
+    if constexpr (kOp == kWxDsm) R = pw_dsm<false, false>(t1, a1, nw1, t1, a1, 0, a1, nullptr, L);
+    if constexpr (kOp == kWxDsmT2) R = pw_dsm<true, false>(t1, a1, nw1, t2, a2, nw2, a1, nullptr, L);
+    if constexpr (kOp == kWxDsmB1) R = pw_dsm<false, true, 1>(t1, a1, nw1, t1, a1, 0, b, bw, L);
+    if constexpr (kOp == kWxDsmB2) R = pw_dsm<false, true, 2>(t1, a1, nw1, t1, a1, 0, b, bw, L);
+    if constexpr (kOp == kWxDsmB) R = pw_dsm<false, true>(t1, a1, nw1, t1, a1, 0, b, bw, L);
+    if constexpr (kOp == kWxDsmT2B) R = pw_dsm<true, true>(t1, a1, nw1, t2, a2, nw2, b, bw, L);
+    Opw(0, R);
+    uint32_t e[8];
+    encode1_wide(e, R);
+    Oenc(4, e);
+  }
+  if constexpr (kOp == kWxEdHalf) {
+    // wide_cores.h eds_chain's two chains from -A (slots 0..3), h and S (slot
+    // 8); word 24: 0 = X (h's windows 0..31 on -A, S's digits 0..7), 1 = Y
+    // (sc_high_half_with_carry(h) on [2^128](-A) doubled as eds_double does,
+    // S's digits 8..15)
+    uint32_t h[8], S[8], a[8];
+    words8(h, 8, 0);
+    words8(S, 8, 8);
+    const bool high = U(8, 24) != 0;
+    pw P = Ipw(0);
+    if (high) {
+#pragma unroll 1
+      for (int k = 0; k < 128; k++) P = pw_dbl(P, L);
+    }
+    TabW t;
+    tab_build(t, P, d2_wide(L), L);
+    pw R;
+    if (high) {
+      sc_high_half_with_carry(a, h);
+      R = pw_dsm<false, true, 2>(t, a, 32, t, a, 0, S, bw, L);
+    } else {
+      R = pw_dsm<false, true, 1>(t, h, 32, t, h, 0, S, bw, L);
+    }
+    Opw(0, R);
+  }
+  if constexpr (kOp == kWxVPart) {
+    // wide_cores.h vrf_sh_split's parts from H (slots 0..3) and s (slot 8);
+    // word 24: the part (0, 1, and 2 with OURO_LAT_V3)
+    uint32_t s[8];
+    words8(s, 8, 0);
+    const int part = (int)U(8, 24);
+    pw Hw = Ipw(0);
+    constexpr int K = OURO_LAT_VWIN, K2 = OURO_LAT_V3 ? OURO_LAT_VWIN2 : 64;
+    int nw = K;
+    if (part != 0) {
+      const int dbl = 4 * (part == 1 ? K : K2);
+#pragma unroll 1
+      for (int k = 0; k < dbl; k++) Hw = pw_dbl(Hw, L);
+      uint32_t hh[8];
+      sc_high_from_window<K>(hh, s);
+      if (OURO_LAT_V3 && part == 2) {
+        sc_high_from_window<(K2 - K) & 63>(s, hh);
+        nw = 64 - K2;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) s[k] = hh[k];
+        nw = K2 - K;
+      }
+    }
+    TabW tab;
+    tab_build(tab, Hw, d2_wide(L), L);
+    Opw(0, pw_dsm<false, false>(tab, s, nw, tab, s, 0, s, nullptr, L));
+  }
+  if constexpr (kOp == kWxBlake) {  // slots 0..7: the digest as this lane holds it
+    uint32_t in[16], h[8];
+#pragma unroll
+    for (int k = 0; k < 16; k++) in[k] = U(0, k);
+    blake2b256_short_quad(h, in, U(0, 16));
+#pragma unroll
+    for (int k = 0; k < 8; k++) O(k, (int32_t)h[k]);
+  }
+}
+#endif
+
+template <int kOp>
+__global__ void __launch_bounds__(64) k_wx_field(int n, const int32_t* in, int32_t* out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if ((int)blockIdx.x >= n) return;  // the whole wave
+  wx_item<kOp>(in + (size_t)blockIdx.x * kWxIn * 64, out + (size_t)blockIdx.x * kWxOut * 64, nullptr);
+#endif
+}
+template <int kOp>
+__global__ void __launch_bounds__(kBlock, OURO_LAT_WAVES) k_wx_core(int n, const int32_t* in, int32_t* out,
+                                                                    const uint16_t* bw) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if ((int)blockIdx.x >= n) return;  // the whole wave
+  wx_item<kOp>(in + (size_t)blockIdx.x * kWxIn * 64, out + (size_t)blockIdx.x * kWxOut * 64, bw);
+#endif
+}
+
+template <int kOp>
+bool wx_launch(int op, int n, const int32_t* in, int32_t* out, const uint16_t* bw) {
+  if (op == kOp) {
+    if constexpr (kOp < kWxFieldOps)
+      hipLaunchKernelGGL(k_wx_field<kOp>, dim3(n), dim3(64), 0, 0, n, in, out);
+    else
+      hipLaunchKernelGGL(k_wx_core<kOp>, dim3(n), dim3(64), 0, 0, n, in, out, bw);
+    return true;
+  }
+  if constexpr (kOp + 1 < kWxOps) return wx_launch<kOp + 1>(op, n, in, out, bw);
+  return false;
+}
+
+// the wide B tables on the device, built as runtime.cpp builds them (the niels
+// tables, then build_btab_wide over them); once per process
+const uint16_t* wx_btab_wide() {
+  static uint16_t* dev = [] {
+    std::vector<int32_t> niels(kBTabWords);
+    build_btab(niels.data());
+    std::vector<int32_t> wide(kBTabWideWords);
+    build_btab_wide(reinterpret_cast<uint16_t*>(wide.data()), niels.data());
+    uint16_t* d = nullptr;
+    if (hipMalloc(&d, sizeof(int32_t) * kBTabWideWords) != hipSuccess) return (uint16_t*)nullptr;
+    if (hipMemcpy(d, wide.data(), sizeof(int32_t) * kBTabWideWords, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      return (uint16_t*)nullptr;
+    }
+    return d;
+  }();
+  return dev;
+}
+
 }  // namespace
 
 extern "C" {
+// Item `op` (enum WxOp) over n records, one wave each: in n * kWxIn * 64 int32,
+// out n * kWxOut * 64 int32 (zeroed first).  0, -1 on bad arguments (a chain
+// item's window counts beyond 64, or scalars beyond the chains' 2^253, are
+// refused here: the kernels index tables with their digits), -2 on a HIP error
+int ouro_wx_params(int* kin, int* kout, int* vwin, int* vwin2, int* v3, int* nops) {
+  *kin = kWxIn;
+  *kout = kWxOut;
+  *vwin = OURO_LAT_VWIN;
+  *vwin2 = OURO_LAT_VWIN2;
+  *v3 = OURO_LAT_V3;
+  *nops = kWxOps;
+  return 0;
+}
+int ouro_wx_op(int op, int n, const int32_t* in, int32_t* out) {
+  if (n <= 0 || !in || !out || op < 0 || op >= kWxOps) return -1;
+  const bool chain = op >= kWxDsm && op <= kWxVPart;
+  for (int i = 0; chain && i < n; i++) {
+    const int32_t* s = in + ((size_t)i * kWxIn + 8) * 64;
+    if ((uint32_t)s[24] > 64u || (uint32_t)s[25] > 64u) return -1;
+    if (((uint32_t)s[7] | (uint32_t)s[15] | (uint32_t)s[23]) >> 29) return -1;
+  }
+  const uint16_t* bw = nullptr;
+  if (chain && !(bw = wx_btab_wide())) return -2;
+  const size_t nin = (size_t)n * kWxIn * 64, nout = (size_t)n * kWxOut * 64;
+  int32_t *d_in = nullptr, *d_out = nullptr;
+  int rc = 0;
+  if (hipMalloc(&d_in, 4 * nin) != hipSuccess || hipMalloc(&d_out, 4 * nout) != hipSuccess) rc = -2;
+  if (!rc && (hipMemcpy(d_in, in, 4 * nin, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemset(d_out, 0, 4 * nout) != hipSuccess))
+    rc = -2;
+  if (!rc) {
+    if (!wx_launch<0>(op, n, d_in, d_out, bw)) rc = -1;
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = -2;
+  }
+  if (!rc && hipMemcpy(out, d_out, 4 * nout, hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
 // SHA-512(pre_i || msg_i[0..len_i)) for n messages on the device, one wave
 // each (pre: 64 B each; msg: 1024-B stride, len_i <= 943); 0 / -1 / -2
 int ouro_wide_sha512_prefixed(int n, const uint8_t* pre, const uint8_t* msg, const uint32_t* len,
