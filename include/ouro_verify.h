@@ -1382,6 +1382,110 @@ int ouro_leader_check_batch_device(void *stream, size_t n, const uint8_t *beta,
                                    int64_t act_log_hi, uint64_t act_log_lo, int f_is_one,
                                    uint8_t *verdict);
 
+/* ---- The forging side: PraosVRF evalCertified and checkIsLeader -------------
+ *
+ * The other half of the reference's `ConsensusProtocol (TPraos c)` instance:
+ * checkIsLeader (ouroboros-consensus-shelley/src/Ouroboros/Consensus/Shelley/
+ * Protocol.hs:366-413) evaluates the leader VRF on mkSeed seedL slot eta0 with
+ * the pool's VRF signing key (VRF.evalCertified), decides meetsLeaderThreshold
+ * (:473-491) or the overlay branch (lookupInOverlaySchedule, :368-399), and
+ * hands back the two certified VRFs a forged header carries.  A pool operator
+ * runs it once per epoch over all of the epoch's slots.  KES signing and block
+ * forging are not offered.
+ *
+ * Every entry validates its arguments before anything runs (OURO_EINVAL: a
+ * NULL array with nonzero n; a span outside alpha_bytes; nkeys not 1 or n;
+ * sigma or act_log outside ouro_leader_check_batch's domain; d_num > d_den,
+ * d_den == 0, or d_num > 0 with asc_inv == 0, ngen == 0 or first_slot before
+ * epoch_first_slot; a slot range whose last slot passes 2^64 - 1).  n == 0
+ * returns OURO_OK.  A device error recomputes on the host path as for every
+ * other host-buffer batch, unless OURO_ON_DEVICE_ERROR=fail.  The *_host
+ * entries run the same lane routines on the host's worker pool.
+ *
+ * A VRF signing key is libsodium's: sk = seed (32) || pk (32).  The scalar is
+ * SHA-512(seed)[0:32], clamped; the public key bytes are used AS GIVEN, as
+ * crypto_vrf_ietfdraft03_prove does (it never recomputes the key).
+ *
+ * KEY HYGIENE.  A key and its expansion live in call-local host memory, in a
+ * launch's arguments, or in a device buffer this call owns.  Before the call
+ * returns the library zeroes every buffer of its own that held them: the
+ * launch's argument block, the key's staging buffer on the device, the
+ * scalars and recoding carries in the per-lane scratch slots, and, on the
+ * host path, the prover's locals (the expanded key, the nonce and what it was
+ * hashed from, the unreduced k + c x).  Nothing of a key reaches
+ * ouro_last_error.  Outside the library's reach, and not claimed: copies the
+ * compiler makes (registers, spill slots, inlined temporaries such as a hash's
+ * message schedule) on the host or the device, the device's registers and the
+ * memory the HIP runtime manages for their spills, and the runtime's own
+ * staging of a host-to-device copy.  NO
+ * constant-time or side-channel claim is made: the device and host routines
+ * index per-lane tables by digits of the secret scalar and branch on them.
+ * These entries are for a machine that already holds the key.
+ *
+ * Pinned: the IETF draft-03 vectors, the oracle's prover and a prover built
+ * from libsodium 1.0.18's primitives, byte for byte (tests/test_prove_rule.py).
+ * Not pinned: mkSeed's composition and checkLeaderValue stay "parity unpinned"
+ * as for the verifying entries; the overlay classification is pinned only to
+ * the Python restatement (ledger.py). */
+
+/* n certified VRFs.  sk: nkeys x 64, nkeys = 1 (one key for every item) or n.
+ * alpha of item i: alpha[alpha_off[i] .. + alpha_len[i]).  proof: n x 80;
+ * beta (may be NULL): n x 64, the outputs (proof_to_hash of each proof). */
+int ouro_vrf03_prove_batch(size_t n, const uint8_t *sk, size_t nkeys, const uint8_t *alpha,
+                           size_t alpha_bytes, const uint64_t *alpha_off,
+                           const uint32_t *alpha_len, uint8_t *proof, uint8_t *beta);
+int ouro_vrf03_prove_batch_host(size_t n, const uint8_t *sk, size_t nkeys, const uint8_t *alpha,
+                                size_t alpha_bytes, const uint64_t *alpha_off,
+                                const uint32_t *alpha_len, uint8_t *proof, uint8_t *beta);
+/* one proof on the host path (crypto_vrf_ietfdraft03_prove's arguments) */
+int ouro_vrf03_prove(uint8_t proof[80], const uint8_t sk[64], const uint8_t *m, size_t mlen);
+/* pk = [clamp(SHA-512(seed)[0:32])]B and sk = seed || pk, on the host path
+ * (crypto_vrf_ietfdraft03_keypair_from_seed's arguments) */
+int ouro_vrf03_keypair_from_seed(uint8_t pk[32], uint8_t sk[64], const uint8_t seed[32]);
+
+/* checkIsLeader for slots first_slot .. first_slot + n_slots - 1 of one epoch */
+#define OURO_SLOT_NOT_LEADER 0u
+#define OURO_SLOT_LEADER 1u           /* a Praos slot, meetsLeaderThreshold */
+#define OURO_SLOT_OVERLAY_ACTIVE 2u   /* gen_index[i] = the scheduled genesis key's index */
+#define OURO_SLOT_OVERLAY_INACTIVE 3u /* NonActiveSlot: nobody may forge */
+typedef struct ouro_leader_params {
+  const uint8_t *epoch_nonce; /* 32 B, NULL = NeutralNonce */
+  uint64_t epoch_first_slot;  /* overlay positions count from here; read only when d_num > 0 */
+  uint64_t sigma_num;         /* the pool's relative stake */
+  uint64_t sigma_den;
+  int64_t act_log_hi;         /* as ouro_leader_check_batch */
+  uint64_t act_log_lo;
+  int f_is_one;
+  uint64_t d_num;             /* decentralisation parameter; d_num = 0: no overlay */
+  uint64_t d_den;
+  uint64_t asc_inv;           /* as ouro_genesis_delegs; read only when d_num > 0 */
+  uint32_t ngen;              /* genesis keys of the epoch; read only when d_num > 0 */
+} ouro_leader_params;
+/* cls: n_slots bytes, OURO_SLOT_*.  gen_index (may be NULL): n_slots, the
+ * index on an OURO_SLOT_OVERLAY_ACTIVE slot, OURO_LV_NO_POOL elsewhere --
+ * whether the pool is that key's delegate is the caller's map lookup
+ * (:385-399).  beta_leader (may be NULL): n_slots x 64, the leader VRF's
+ * output, filled for EVERY class (on an overlay slot the reference evaluates
+ * it "as normal"; no threshold applies there).  The host sits between this
+ * call and ouro_tpraos_leader_vrfs on purpose: the winners are a few percent
+ * of the slots. */
+int ouro_tpraos_leader_schedule(const uint8_t vrf_sk[64], const ouro_leader_params *p,
+                                uint64_t first_slot, size_t n_slots, uint8_t *cls,
+                                uint32_t *gen_index, uint8_t *beta_leader);
+int ouro_tpraos_leader_schedule_host(const uint8_t vrf_sk[64], const ouro_leader_params *p,
+                                     uint64_t first_slot, size_t n_slots, uint8_t *cls,
+                                     uint32_t *gen_index, uint8_t *beta_leader);
+/* TPraosIsLeader's two certified VRFs for m chosen slots (rho and y of
+ * Protocol.hs:409-413): the proofs of mkSeed seedEta / seedL slot[j]
+ * epoch_nonce (NULL = NeutralNonce), m x 80 each, and their outputs, m x 64
+ * each (either may be NULL). */
+int ouro_tpraos_leader_vrfs(const uint8_t vrf_sk[64], const uint8_t *epoch_nonce, size_t m,
+                            const uint64_t *slot, uint8_t *eta_proof, uint8_t *eta_output,
+                            uint8_t *leader_proof, uint8_t *leader_output);
+int ouro_tpraos_leader_vrfs_host(const uint8_t vrf_sk[64], const uint8_t *epoch_nonce, size_t m,
+                                 const uint64_t *slot, uint8_t *eta_proof, uint8_t *eta_output,
+                                 uint8_t *leader_proof, uint8_t *leader_output);
+
 #ifdef __cplusplus
 }
 #endif

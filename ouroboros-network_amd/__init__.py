@@ -17,11 +17,13 @@ from .header import (chain_envelope_cbor, validate_chain_cbor, validate_chain_le
 from .ledger import (Counters, GenesisDelegs, Globals, LedgerViews, counter_fold,
                      ledger_checks)
 from .kes import Sum6KES, kes_period
+from .leader import ActiveSlotCoeff, leader_schedule, leader_vrfs
 from .tpraos import EpochNonces, HeaderBatch, first_invalid, verify_headers, verify_headers_multi
 from .vrf import PraosVRF
 from .witness import count_block_witnesses, parse_witnesses, verify_block_witnesses
 
 __all__ = [
+    "ActiveSlotCoeff",
     "ByronDSIGN",
     "Counters",
     "DeviceError",
@@ -40,6 +42,8 @@ __all__ = [
     "counter_fold",
     "first_invalid",
     "kes_period",
+    "leader_schedule",
+    "leader_vrfs",
     "ledger_checks",
     "dlg_cert_message",
     "pack_byron_cbor",

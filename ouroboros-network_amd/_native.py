@@ -65,6 +65,11 @@ LV_NO_POOL = 0xFFFFFFFF
 LV_ROWS_MAX = 1 << 24
 LV_GEN_ROWS_MAX = 1 << 16
 
+SLOT_NOT_LEADER = 0       # ouro_tpraos_leader_schedule cls[i]
+SLOT_LEADER = 1
+SLOT_OVERLAY_ACTIVE = 2
+SLOT_OVERLAY_INACTIVE = 3
+
 LEADER_NO = 0
 LEADER_YES = 1
 LEADER_BADARG = 0xFF
@@ -159,6 +164,17 @@ class OcertCountersC(ctypes.Structure):
 
     _fields_ = [("m", ctypes.c_size_t), ("pool_id", ctypes.c_void_p),
                 ("counter", ctypes.c_void_p), ("present", ctypes.c_void_p)]
+
+
+class LeaderParamsC(ctypes.Structure):
+    """Mirror of ``ouro_leader_params`` (include/ouro_verify.h)."""
+
+    _fields_ = [("epoch_nonce", ctypes.c_void_p), ("epoch_first_slot", ctypes.c_uint64),
+                ("sigma_num", ctypes.c_uint64), ("sigma_den", ctypes.c_uint64),
+                ("act_log_hi", ctypes.c_int64), ("act_log_lo", ctypes.c_uint64),
+                ("f_is_one", ctypes.c_int), ("d_num", ctypes.c_uint64),
+                ("d_den", ctypes.c_uint64), ("asc_inv", ctypes.c_uint64),
+                ("ngen", ctypes.c_uint32)]
 
 
 class GenesisDelegsC(ctypes.Structure):
@@ -357,6 +373,16 @@ SIGNATURES = {
     "ouro_leader_check_batch": (_I, [_SZ, _P, _P, _P, ctypes.c_int64, ctypes.c_uint64, _I, _P]),
     "ouro_leader_check_batch_device": (_I, [_P, _SZ, _P, _P, _P, ctypes.c_int64, ctypes.c_uint64,
                                             _I, _P]),
+    "ouro_vrf03_prove_batch": (_I, [_SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
+    "ouro_vrf03_prove_batch_host": (_I, [_SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
+    "ouro_vrf03_prove": (_I, [_P, _P, _P, _SZ]),
+    "ouro_vrf03_keypair_from_seed": (_I, [_P, _P, _P]),
+    "ouro_tpraos_leader_schedule": (_I, [_P, ctypes.POINTER(LeaderParamsC), ctypes.c_uint64, _SZ,
+                                         _P, _P, _P]),
+    "ouro_tpraos_leader_schedule_host": (_I, [_P, ctypes.POINTER(LeaderParamsC), ctypes.c_uint64,
+                                              _SZ, _P, _P, _P]),
+    "ouro_tpraos_leader_vrfs": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
+    "ouro_tpraos_leader_vrfs_host": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P]),
     "ouro_nonce_fold": (_I, [_SZ, _P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P]),
     "ouro_tpraos_pack_bytes": (_SZ, [_SZ]),
     "ouro_tpraos_pack_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, _P, _SZ,

@@ -14,6 +14,7 @@
 #include "lane_items.h"
 #include "leader.h"
 #include "ledger_view.h"
+#include "prove.h"
 #include "tpraos.h"
 #include "wide_cores.h"
 
@@ -547,6 +548,22 @@ int dh_btab_wide_entry(int half, int idx, uint16_t out[kBWideU16]) {
     return t;
   }();
   memcpy(out, tab.data() + ((size_t)half * kBTabEntries + idx) * kBWideU16, sizeof(uint16_t) * kBWideU16);
+  return 0;
+}
+
+// [k]P through the prover's scalar chain (prove.h var_mul): P from its
+// encoding; reduce != 0: k is a clamped scalar, reduced mod L first as the
+// prover does (expand_seed_scalar).  -1 when P does not decode.
+int dh_var_mul(uint8_t* out, const uint8_t* k, const uint8_t* point, int reduce) {
+  uint32_t kw[8], kr[8], pw[8], enc[8];
+  bytes_to_words8(kw, k);
+  bytes_to_words8(pw, point);
+  ge_p3 P;
+  if (!ge_decode(&P, pw, false)) return -1;
+  if (reduce) sc_reduce256(kr, kw);
+  Lane lane;
+  encode_p2(enc, var_mul(reduce ? kr : kw, P, lane.s, host_btab()));
+  memcpy(out, enc, 32);
   return 0;
 }
 }

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/ouro_verify.h"
+#include "forge_args.h"
 
 namespace ouro_host {
 
@@ -42,6 +43,20 @@ int leader_batch(size_t n, const uint8_t* beta, const uint64_t* num, const uint6
                  int64_t act_log_hi, uint64_t act_log_lo, int f_is_one, uint8_t* verdict);
 // proof_to_hash without verification: OURO_OK and out written, or OURO_INVALID
 int proof_to_hash(uint8_t* out, const uint8_t* proof);
+
+// The forging side (forge.h), the same item routines as kernels_forge.hip's
+// kernels and the same arguments as launches.h launch_leader_schedule /
+// launch_vrf_prove, over host memory at any alignment.  A worker's lane is
+// cleared of the scalars after every item.
+int sched_batch(const OuroForgeSched& s, uint64_t first_slot, size_t n, uint8_t* cls,
+                uint32_t* gen_index, uint8_t* beta);
+int prove_batch(size_t n, const uint8_t* sk, bool shared_key, const uint8_t* alpha,
+                const uint64_t* off, const uint32_t* len, const uint64_t* slot,
+                const uint8_t* eta0, uint8_t* proof, uint8_t* beta);
+// x (the clamped scalar of sk's seed, reduced mod L) and the key bytes of sk
+void sched_key(OuroForgeSched* s, const uint8_t sk[64]);
+// pk = [clamp(SHA-512(seed)[0:32])]B
+void vrf_public_key(uint8_t pk[32], const uint8_t seed[32]);
 
 // Threads a batch of n items uses (OURO_HOST_THREADS caps it; default: the
 // CPUs this process may run on, at most 64, and at least 16 items each).

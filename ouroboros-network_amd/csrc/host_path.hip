@@ -4,7 +4,9 @@
 // for line (k_ed25519_verify, k_vrf03_verify with its strict-s rule,
 // k_sum6kes_verify, k_tpraos_verify, k_leader_check, k_vrf03_proof_to_hash),
 // so a host verdict is the device verdict: tests/test_host_path.py pins both
-// against the oracle on the same edge-case sets.
+// against the oracle on the same edge-case sets.  The forging side
+// (kernels_forge.hip k_leader_schedule, k_vrf03_prove) is mirrored the same
+// way, through forge.h's items.
 // its own host copies of the out-of-line lane routines (common.h)
 #define OURO_NI_LINKAGE static
 
@@ -16,6 +18,7 @@
 #include <new>
 #include <vector>
 
+#include "forge.h"
 #include "host_fast.h"
 #include "host_path.h"
 #include "knobs.h"
@@ -252,6 +255,67 @@ int leader_batch(size_t n, const uint8_t* beta, const uint64_t* num, const uint6
                                                    act_log_hi);
     verdict[i] = r < 0 ? (uint8_t)0xff : (uint8_t)r;
   });
+}
+
+// ---- the forging side: forge.h's items, as kernels_forge.hip runs them ----
+int sched_batch(const OuroForgeSched& s, uint64_t first_slot, size_t n, uint8_t* cls,
+                uint32_t* gen_index, uint8_t* beta) {
+  const int32_t* bt = btab();
+  return parallel_items(n, [&](size_t i, Slot lane) {
+    uint32_t b[16], gi;
+    cls[i] = forge_schedule_item(s, first_slot + i, b, &gi, lane, bt);
+    if (gen_index) gen_index[i] = gi;
+    if (beta) st_words(beta + 64 * i, b, 4);
+    prove_wipe_lane(lane);
+  });
+}
+
+int prove_batch(size_t n, const uint8_t* sk, bool shared_key, const uint8_t* alpha,
+                const uint64_t* off, const uint32_t* len, const uint64_t* slot,
+                const uint8_t* eta0, uint8_t* proof, uint8_t* beta) {
+  const int32_t* bt = btab();
+  return parallel_items(n, [&](size_t i, Slot lane) {
+    uint32_t k[16], pi[20], b[16];
+    ld_words(k, sk + (shared_key ? 0 : 64 * i), 4);
+    if (slot) {
+      uint32_t e0[8];
+      if (eta0) ld_words(e0, eta0, 2);
+      ProveRegTail a;
+      forge_seed(a.w, slot[i >> 1], eta0 ? e0 : nullptr, (i & 1) != 0);
+      forge_prove_item(pi, beta ? b : nullptr, k, a, 32, lane, bt);
+    } else {
+      forge_prove_item(pi, beta ? b : nullptr, k, ShaGlobalTail{alpha + off[i]}, len[i], lane, bt);
+    }
+    st_words(proof + 80 * i, pi, 5);
+    if (beta) st_words(beta + 64 * i, b, 4);
+    prove_wipe_lane(lane);
+    prove_wipe(k, sizeof k);
+  });
+}
+
+void sched_key(OuroForgeSched* s, const uint8_t sk[64]) {
+  uint32_t w[16];
+  ExpandedKey k;
+  ld_words(w, sk, 4);
+  expand_vrf_sk(k, w);
+  for (int i = 0; i < 8; i++) {
+    s->x[i] = k.a[i];
+    s->pk[i] = k.pk[i];
+  }
+  prove_wipe(w, sizeof w);
+  prove_wipe(&k, sizeof k);
+}
+
+void vrf_public_key(uint8_t pk[32], const uint8_t seed[32]) {
+  uint32_t w[8];
+  ExpandedKey k;
+  ld_words(w, seed, 2);
+  HostLane& l = thread_lane();
+  expand_seed(k, w, l.s, btab());
+  st_words(pk, k.pk, 2);
+  prove_wipe_lane(l.s);
+  prove_wipe(w, sizeof w);
+  prove_wipe(&k, sizeof k);
 }
 
 int proof_to_hash(uint8_t* out, const uint8_t* proof) {

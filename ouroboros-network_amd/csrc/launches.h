@@ -9,6 +9,7 @@
 #include "cbor.h"
 #include "cbor_block.h"
 #include "cbor_byron.h"
+#include "forge_args.h"
 
 // the byte ranges of a plan window's copy kernel (kernels.hip
 // k_plan_stage_ranges), filled by ouro_tpraos_plan_submit (plan.cpp)
@@ -151,6 +152,21 @@ int launch_witness_verify(hipStream_t st, size_t wit_cap, const uint64_t* rows, 
 int launch_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
                           const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
                           uint8_t* verdict, uint32_t* n_bad);
+
+// the forging-side kernels (kernels_forge.hip; forge.h), each checking its own
+// launch, on k_ed25519_verify's launch shape and scratch slots.  Every pointer
+// is device memory, 16-byte aligned.
+// checkIsLeader for slots first_slot .. first_slot + n - 1: cls (n bytes),
+// gen_index (n, optional), beta (n x 64, optional); s travels with the launch
+int launch_leader_schedule(hipStream_t st, const OuroForgeSched& s, uint64_t first_slot, size_t n,
+                           uint8_t* cls, uint32_t* gen_index, uint8_t* beta);
+// n certified VRFs: sk n x 64, or one row when shared_key.  slot null: alpha
+// spans (off / len; the buffer allocated up to the next multiple of 4).  Else
+// item i proves mkSeed(seedEta for even i, seedL for odd i, slot[i / 2], eta0)
+// (eta0: 32 bytes, null = NeutralNonce).  proof n x 80; beta n x 64, optional
+int launch_vrf_prove(hipStream_t st, size_t n, const uint8_t* sk, bool shared_key,
+                     const uint8_t* alpha, const uint64_t* off, const uint32_t* len,
+                     const uint64_t* slot, const uint8_t* eta0, uint8_t* proof, uint8_t* beta);
 
 }  // namespace ouro_rt
 #pragma GCC visibility pop

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass
 from fractions import Fraction
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -28,6 +28,10 @@ from ._pack import ptr
 LEADER_NO = _native.LEADER_NO
 LEADER_YES = _native.LEADER_YES
 LEADER_BADARG = _native.LEADER_BADARG
+SLOT_NOT_LEADER = _native.SLOT_NOT_LEADER
+SLOT_LEADER = _native.SLOT_LEADER
+SLOT_OVERLAY_ACTIVE = _native.SLOT_OVERLAY_ACTIVE
+SLOT_OVERLAY_INACTIVE = _native.SLOT_OVERLAY_INACTIVE
 
 
 @dataclass(frozen=True)
@@ -81,3 +85,80 @@ def check_leader_value(beta: bytes, sigma: Fraction, f: ActiveSlotCoeff) -> bool
     if v[0] == LEADER_BADARG:
         raise ValueError("sigma or active slot coefficient outside the supported domain")
     return bool(v[0] == LEADER_YES)
+
+
+def _fraction64(x, what: str) -> Fraction:
+    x = Fraction(x)
+    if x.numerator < 0 or x.denominator >= 1 << 64 or x.numerator >= 1 << 64:
+        raise ValueError(f"{what} must be a non-negative fraction of 64-bit integers")
+    return x
+
+
+def _nonce_arg(epoch_nonce: Optional[bytes]):
+    if epoch_nonce is None:
+        return None, None
+    if len(epoch_nonce) != 32:
+        raise ValueError("an epoch nonce is 32 bytes (None = NeutralNonce)")
+    buf = np.frombuffer(bytes(epoch_nonce), dtype=np.uint8).copy()
+    return buf, ptr(buf)
+
+
+def leader_schedule(vrf_sk: bytes, epoch_nonce: Optional[bytes], first_slot: int, n_slots: int,
+                    sigma: Fraction, f: ActiveSlotCoeff, d=Fraction(0),
+                    asc_inv: Optional[int] = None, ngen: int = 0,
+                    epoch_first_slot: Optional[int] = None, host: bool = False):
+    """``checkIsLeader`` (Shelley/Protocol.hs:366-413) for slots ``first_slot ..
+    first_slot + n_slots - 1`` of one epoch under the pool's VRF signing key
+    (64 bytes, seed || pk) and relative stake ``sigma``.  Returns ``(cls,
+    gen_index, beta_leader)``: the SLOT_* class of every slot (u8), the
+    scheduled genesis key's index on an active overlay slot (u32, LV_NO_POOL
+    elsewhere) and the leader VRF's output for every slot ((n, 64) u8).
+
+    ``d`` is the decentralisation parameter; with ``d > 0`` the overlay
+    schedule needs ``asc_inv`` (1 / f) and ``ngen`` (the epoch's genesis keys),
+    and positions count from ``epoch_first_slot`` (default: ``first_slot``).
+    host=True: ouro_tpraos_leader_schedule_host instead of the GPU."""
+    if len(vrf_sk) != 64:
+        raise ValueError("a VRF signing key is 64 bytes (seed || pk)")
+    sigma = _fraction64(sigma, "sigma")
+    d = _fraction64(d, "d")
+    hi, lo = f.words()
+    nonce_buf, nonce_ptr = _nonce_arg(epoch_nonce)
+    p = _native.LeaderParamsC(
+        epoch_nonce=nonce_ptr,
+        epoch_first_slot=first_slot if epoch_first_slot is None else epoch_first_slot,
+        sigma_num=sigma.numerator, sigma_den=sigma.denominator, act_log_hi=hi, act_log_lo=lo,
+        f_is_one=1 if f.is_one else 0, d_num=d.numerator, d_den=d.denominator,
+        asc_inv=0 if asc_inv is None else asc_inv, ngen=ngen)
+    cls = np.zeros(n_slots, dtype=np.uint8)
+    gen = np.full(n_slots, _native.LV_NO_POOL, dtype=np.uint32)
+    beta = np.zeros((n_slots, 64), dtype=np.uint8)
+    if n_slots:
+        name = "ouro_tpraos_leader_schedule" + ("_host" if host else "")
+        rc = getattr(_native.load(), name)(bytes(vrf_sk), ctypes.byref(p),
+                                           ctypes.c_uint64(first_slot), n_slots, ptr(cls),
+                                           ptr(gen), ptr(beta))
+        _native.check(rc, name)
+    return cls, gen, beta
+
+
+def leader_vrfs(vrf_sk: bytes, epoch_nonce: Optional[bytes], slots, host: bool = False):
+    """``TPraosIsLeader``'s two certified VRFs (rho and y of Protocol.hs:409-413)
+    for the chosen ``slots``: ``(eta_proof (m, 80), eta_output (m, 64),
+    leader_proof (m, 80), leader_output (m, 64))`` u8.  host=True:
+    ouro_tpraos_leader_vrfs_host instead of the GPU."""
+    if len(vrf_sk) != 64:
+        raise ValueError("a VRF signing key is 64 bytes (seed || pk)")
+    slot = np.ascontiguousarray(np.asarray(slots, dtype=np.uint64).reshape(-1))
+    m = slot.shape[0]
+    nonce_buf, nonce_ptr = _nonce_arg(epoch_nonce)
+    ep = np.zeros((m, 80), dtype=np.uint8)
+    eo = np.zeros((m, 64), dtype=np.uint8)
+    lp = np.zeros((m, 80), dtype=np.uint8)
+    lo = np.zeros((m, 64), dtype=np.uint8)
+    if m:
+        name = "ouro_tpraos_leader_vrfs" + ("_host" if host else "")
+        rc = getattr(_native.load(), name)(bytes(vrf_sk), nonce_ptr, m, ptr(slot), ptr(ep),
+                                           ptr(eo), ptr(lp), ptr(lo))
+        _native.check(rc, name)
+    return ep, eo, lp, lo
