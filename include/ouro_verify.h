@@ -678,9 +678,10 @@ int ouro_byron_pack_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *o
  * ByronDSIGN batch verify of the packed rows on the calling thread's stream.
  * verdict[i] = 1 for a regular header whose block signature verifies and for
  * an epoch-boundary header (PBftValidateBoundary checks nothing), else 0;
- * status[i] as above.  The delegation lookup and the signing-window
- * threshold (PBFT.hs:344-357) stay with the caller: they are ledger state,
- * not crypto. */
+ * status[i] as above.  The delegation lookup, the slot check and the
+ * signing-window threshold (PBFT.hs:340-357) are not part of this call:
+ * ouro_pbft_ledger_checks below evaluates them over the sliced rows
+ * (ouro_byron_pack_cbor's delegate_vk and status, and the slots). */
 int ouro_byron_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
                            const uint32_t *len, size_t n, int64_t protocol_magic,
                            uint8_t *status, uint8_t *verdict);
@@ -1149,6 +1150,172 @@ int ouro_chain_validate_ledger_overlay_cbor_host(
     const ouro_genesis_delegs *genesis, const ouro_ledger_globals *globals,
     const ouro_ocert_counters *counters, uint64_t *counter_out, uint8_t *present_out,
     uint8_t *ledger, uint32_t *pool_row);
+
+/* --------------------------------- Byron ledger-view checks (PBFT) --------- */
+/* What the reference's PBFT instance checks per regular Byron header beside
+ * the block signature (ouroboros-consensus/src/Ouroboros/Consensus/Protocol/
+ * PBFT.hs:322-357), as OURO_PBFT_* bits -- all of them, where the reference
+ * stops at the first failure (the OURO_LV_* convention):
+ *   DELEGATE_KNOWN  hashVerKey of the header's delegate key is a delegate in
+ *                   the entry's delegation map (Bimap.lookupR; else
+ *                   PBftNotGenesisDelegate).  hashVerKey is CC.Common.hashKey:
+ *                   KH(k) = Blake2b-224(SHA3-256(0x58 0x40 || k)) over the 64
+ *                   XPub bytes (ouro_byron_key_hash_batch).
+ *   SLOT_OK         the slot does not go back behind the last signed slot; the
+ *                   inequality is non-strict (else PBftInvalidSlot)
+ *   WINDOW_OK       the delegate's genesis key has signed at most `threshold`
+ *                   of the last `window` blocks, this one included
+ *                                             (else PBftExceededSignThreshold)
+ *   BOUNDARY        an epoch-boundary header (status OURO_PACK_EBB):
+ *                   PBftValidateBoundary checks nothing and leaves the state
+ *                   alone; the row is BOUNDARY | ALL_OK, so a caller's
+ *                   acceptance test is one mask on either kind of row.
+ * A TPraos or unsliced row gets 0.  The bits do not depend on the signature
+ * verdict.  DELEGATE_KNOWN and BOUNDARY are evaluated per row, in parallel
+ * (k_pbft_checks, one row per lane); SLOT_OK and WINDOW_OK by the sequential
+ * fold ouro_pbft_window_fold on the host. */
+#define OURO_PBFT_DELEGATE_KNOWN 0x01u
+#define OURO_PBFT_SLOT_OK 0x02u
+#define OURO_PBFT_WINDOW_OK 0x04u
+#define OURO_PBFT_BOUNDARY 0x08u
+#define OURO_PBFT_ALL_OK 0x07u
+/* A delegation schedule, shaped like ouro_ledger_views: entry j applies to
+ * first_slot[j] <= slot (the last such entry, by the same binary search).
+ * Entry j's delegation map is rows dlg_begin[j] .. dlg_begin[j + 1] of the
+ * flat arrays: (delegate id, genesis id) pairs sorted by the 28 delegate id
+ * bytes as unsigned bytes, strictly ascending; the genesis ids of an entry are
+ * distinct too (the reference's map is a Bimap).  window >= 1 and threshold
+ * are the reference's PBftWindowParams; floor(pbftSignatureThreshold * k)
+ * (PBFT.hs:396-398, a Double product) is the caller's to compute.
+ * OURO_EINVAL before anything runs: k outside 1 .. OURO_EPOCHS_MAX,
+ * first_slot[0] != 0 or not strictly increasing, dlg_begin[0] != 0 or
+ * decreasing, more than OURO_LV_GEN_ROWS_MAX rows, delegate ids out of order,
+ * a genesis id twice in an entry, window == 0, a NULL array. */
+typedef struct ouro_pbft_views {
+  size_t k;
+  const uint64_t *first_slot; /* k                                              */
+  const uint32_t *dlg_begin;  /* k + 1                                          */
+  const uint8_t *delegate_id; /* rows x 28  KH of the delegate's XPub, sorted   */
+  const uint8_t *genesis_id;  /* rows x 28  KH of the genesis key it signs for  */
+  uint64_t window;            /* >= 1                                           */
+  uint64_t threshold;
+} ouro_pbft_views;
+/* The signing window a chain state holds (PBftState's inWindow): n <= window
+ * signers, oldest first, each the genesis id and the slot it signed in.
+ * OURO_EINVAL: n > window, a NULL array with n > 0. */
+typedef struct ouro_pbft_state {
+  size_t n;
+  const uint8_t *signer_id;    /* n x 28  genesis ids */
+  const uint64_t *signer_slot; /* n                   */
+} ouro_pbft_state;
+
+/* KH of n XPubs (n x 64 -> n x 28): what a caller builds a schedule's ids
+ * with.  One key per lane on the GPU (k_byron_key_hash); a device error
+ * recomputes on the host path; _host is the host path alone; _device: device
+ * pointers (4-byte aligned) on the caller's stream, not synchronised. */
+int ouro_byron_key_hash_batch(size_t n, const uint8_t *xpub, uint8_t *out);
+int ouro_byron_key_hash_batch_host(size_t n, const uint8_t *xpub, uint8_t *out);
+int ouro_byron_key_hash_batch_device(void *stream, size_t n, const uint8_t *xpub, uint8_t *out);
+
+/* The window fold (PBFT/State.hs:207-229 append, PBFT.hs:340-357) over n rows
+ * in stream order, on the host, exact; the sibling of ouro_ocert_counter_fold
+ * and ouro_nonce_fold.  A row with OURO_PBFT_DELEGATE_KNOWN and without
+ * OURO_PBFT_BOUNDARY in pbft[i] is folded, every other row is left as it is
+ * (signed_count[i] = 0):
+ *   SLOT_OK    iff the window is empty or slot[i] >= the last signer's slot;
+ *   then (slot[i], genesis_id[genesis_row[i]]) is appended, and if the window
+ *   held `window` signers BEFORE the append the oldest is dropped;
+ *   signed_count[i] (may be NULL) = that genesis id's count in the window
+ *   after the trim; WINDOW_OK iff signed_count[i] <= threshold.
+ * The append happens AS GIVEN, whatever the bits and the signature say -- the
+ * way the envelope links to header i - 1 as given; the caller stops at the
+ * first invalid header, and up to and including it the bits equal the
+ * reference's outcome.  Counting is by the 28 id bytes: an incoming signer
+ * whose id no entry knows still counts.  The window afterwards goes to
+ * signer_id_out / signer_slot_out (capacity `window` rows each; may alias the
+ * inputs) and *n_out, so calls chain like tip_out.  in == NULL: the empty
+ * window (genesis).  A folded row whose genesis_row[i] lies outside the
+ * schedule (never what the rule gives) appends nothing: its SLOT_OK and
+ * WINDOW_OK come out clear and the window stays as it was. */
+int ouro_pbft_window_fold(size_t n, const uint32_t *genesis_row, const uint64_t *slot,
+                          const ouro_pbft_views *views, const ouro_pbft_state *in,
+                          uint8_t *signer_id_out, uint64_t *signer_slot_out, size_t *n_out,
+                          uint8_t *pbft, uint64_t *signed_count);
+
+/* The rules above for n Byron header rows (SoA host buffers: delegate_vk as
+ * ouro_byron_batch has it, the slots, and status as ouro_byron_pack_cbor gives
+ * it): pbft[i] = OURO_PBFT_* bits, genesis_row[i] (may be NULL) = the absolute
+ * schedule row of the delegate, or OURO_LV_NO_POOL; signed_count (may be
+ * NULL).  state_in == NULL: no fold -- only DELEGATE_KNOWN and BOUNDARY are
+ * evaluated (a boundary row is BOUNDARY | ALL_OK either way) and the state
+ * outputs are unused; otherwise the fold above runs over the results.  A
+ * device error recomputes on the host path; _host is the host path alone. */
+int ouro_pbft_ledger_checks(size_t n, const uint8_t *delegate_vk, const uint64_t *slot,
+                            const uint8_t *status, const ouro_pbft_views *views,
+                            const ouro_pbft_state *state_in, uint8_t *signer_id_out,
+                            uint64_t *signer_slot_out, size_t *n_out, uint8_t *pbft,
+                            uint32_t *genesis_row, uint64_t *signed_count);
+int ouro_pbft_ledger_checks_host(size_t n, const uint8_t *delegate_vk, const uint64_t *slot,
+                                 const uint8_t *status, const ouro_pbft_views *views,
+                                 const ouro_pbft_state *state_in, uint8_t *signer_id_out,
+                                 uint64_t *signer_slot_out, size_t *n_out, uint8_t *pbft,
+                                 uint32_t *genesis_row, uint64_t *signed_count);
+/* Device pointers on the caller's stream, not synchronised, no fold
+ * (delegate_vk and genesis_row 4-byte aligned, slot 8-byte aligned;
+ * genesis_row required).  The schedule is checked, packed and uploaded once by
+ * ouro_pbft_views_upload (synchronous; on the calling thread's device) and
+ * released by ouro_pbft_views_free. */
+typedef struct ouro_pbft_views_dev ouro_pbft_views_dev;
+int ouro_pbft_views_upload(const ouro_pbft_views *views, ouro_pbft_views_dev **out);
+void ouro_pbft_views_free(ouro_pbft_views_dev *dv);
+int ouro_pbft_ledger_checks_device(void *stream, size_t n, const uint8_t *delegate_vk,
+                                   const uint64_t *slot, const uint8_t *status,
+                                   const ouro_pbft_views_dev *views, uint8_t *pbft,
+                                   uint32_t *genesis_row);
+
+/* ouro_chain_validate_ledger_overlay_cbor with the Byron ledger-view checks in
+ * the same call: every argument and result of that entry, unchanged, then the
+ * delegation schedule, the window in and out (pbft_state_in may be NULL: no
+ * fold, and the three state outputs are unused), pbft[n], genesis_row_pbft[n]
+ * (may be NULL) and signed_count[n] (may be NULL).  With pbft_views NULL it is
+ * the overlay entry, byte for byte, and the arguments after it are unused.  A
+ * TPraos or unsliced row gets pbft = 0, row OURO_LV_NO_POOL, count 0.  The
+ * slot of a Byron row is the envelope's: epoch * cfg->byron_epoch_slots + slot
+ * in epoch.  How it runs: the schedule is packed and uploaded once per call
+ * behind the same event as the ledger views; on a chunk's stream, after the
+ * Byron slicer and the envelope slicer, k_pbft_checks_chain runs over the PBFT
+ * rows already in the slot's arena, reading each row's slot from its envelope
+ * record (a mixed chunk's through its index list); the chunk copies back 13
+ * more bytes per PBFT row (bits, row, and the slot the host's fold needs) and
+ * a mixed chunk scatters them through the existing index list; the window
+ * fold runs in stream order as chunks drain, next to the counter fold.  A
+ * device error recomputes the batch on the host path, this stage included,
+ * the fold restarted from the window as the call found it.  _host: the host
+ * path alone. */
+int ouro_chain_validate_ledger_pbft_cbor(
+    const uint8_t *raw, size_t raw_bytes, const uint64_t *off, const uint32_t *len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+    const uint8_t *eta_alpha, const uint8_t *leader_alpha, const ouro_envelope_cfg *cfg,
+    const ouro_chain_tip *tip_in, uint8_t *proto, uint8_t *status, uint8_t *verdict,
+    uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce, uint8_t *header_hash,
+    uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
+    const ouro_genesis_delegs *genesis, const ouro_ledger_globals *globals,
+    const ouro_ocert_counters *counters, uint64_t *counter_out, uint8_t *present_out,
+    uint8_t *ledger, uint32_t *pool_row, const ouro_pbft_views *pbft_views,
+    const ouro_pbft_state *pbft_state_in, uint8_t *signer_id_out, uint64_t *signer_slot_out,
+    size_t *n_out, uint8_t *pbft, uint32_t *genesis_row_pbft, uint64_t *signed_count);
+int ouro_chain_validate_ledger_pbft_cbor_host(
+    const uint8_t *raw, size_t raw_bytes, const uint64_t *off, const uint32_t *len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces *epochs,
+    const uint8_t *eta_alpha, const uint8_t *leader_alpha, const ouro_envelope_cfg *cfg,
+    const ouro_chain_tip *tip_in, uint8_t *proto, uint8_t *status, uint8_t *verdict,
+    uint8_t *beta_eta, uint8_t *beta_leader, uint8_t *eta_nonce, uint8_t *header_hash,
+    uint8_t *envelope, ouro_chain_tip *tip_out, const ouro_ledger_views *views,
+    const ouro_genesis_delegs *genesis, const ouro_ledger_globals *globals,
+    const ouro_ocert_counters *counters, uint64_t *counter_out, uint8_t *present_out,
+    uint8_t *ledger, uint32_t *pool_row, const ouro_pbft_views *pbft_views,
+    const ouro_pbft_state *pbft_state_in, uint8_t *signer_id_out, uint64_t *signer_slot_out,
+    size_t *n_out, uint8_t *pbft, uint32_t *genesis_row_pbft, uint64_t *signed_count);
 
 /* (How ouro_byron_verify_cbor runs, since round 6: on the raw-CBOR pipeline
  * of ouro_tpraos_verify_cbor -- chunks gathered into pinned NUMA-local

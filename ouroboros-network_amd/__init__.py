@@ -17,6 +17,8 @@ from .header import (chain_envelope_cbor, validate_chain_cbor, validate_chain_le
 from .ledger import (Counters, GenesisDelegs, Globals, LedgerViews, counter_fold,
                      ledger_checks)
 from .kes import Sum6KES, kes_period
+from .pbft import (PBftState, PBftViews, byron_key_hash, pbft_checks, pbft_rule,
+                   pbft_window_fold, validate_chain_pbft_cbor)
 from .leader import ActiveSlotCoeff, leader_schedule, leader_vrfs
 from .tpraos import EpochNonces, HeaderBatch, first_invalid, verify_headers, verify_headers_multi
 from .vrf import PraosVRF
@@ -34,9 +36,12 @@ __all__ = [
     "HeaderBatch",
     "LedgerViews",
     "NativeUnavailable",
+    "PBftState",
+    "PBftViews",
     "PraosVRF",
     "Sum6KES",
     "blake2b256_batch",
+    "byron_key_hash",
     "chain_envelope_cbor",
     "count_block_witnesses",
     "counter_fold",
@@ -50,8 +55,12 @@ __all__ = [
     "parse_block",
     "parse_byron_header",
     "parse_witnesses",
+    "pbft_checks",
+    "pbft_rule",
+    "pbft_window_fold",
     "validate_chain_cbor",
     "validate_chain_ledger_cbor",
+    "validate_chain_pbft_cbor",
     "verify_block_integrity_cbor",
     "verify_block_witnesses",
     "verify_byron_cbor",

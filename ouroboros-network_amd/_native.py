@@ -64,6 +64,11 @@ LV_ALL_OK = 0x1F
 LV_NO_POOL = 0xFFFFFFFF
 LV_ROWS_MAX = 1 << 24
 LV_GEN_ROWS_MAX = 1 << 16
+PBFT_DELEGATE_KNOWN = 0x01  # ouro_pbft_ledger_checks pbft[i]
+PBFT_SLOT_OK = 0x02
+PBFT_WINDOW_OK = 0x04
+PBFT_BOUNDARY = 0x08
+PBFT_ALL_OK = 0x07
 
 SLOT_NOT_LEADER = 0       # ouro_tpraos_leader_schedule cls[i]
 SLOT_LEADER = 1
@@ -185,6 +190,22 @@ class GenesisDelegsC(ctypes.Structure):
                                        "delegate_vrf")] + [("asc_inv", ctypes.c_uint64)]
 
 
+class PBftViewsC(ctypes.Structure):
+    """Mirror of ``ouro_pbft_views`` (include/ouro_verify.h)."""
+
+    _fields_ = [("k", ctypes.c_size_t)] + [
+        (f, ctypes.c_void_p) for f in ("first_slot", "dlg_begin", "delegate_id",
+                                       "genesis_id")] + [("window", ctypes.c_uint64),
+                                                         ("threshold", ctypes.c_uint64)]
+
+
+class PBftStateC(ctypes.Structure):
+    """Mirror of ``ouro_pbft_state`` (include/ouro_verify.h)."""
+
+    _fields_ = [("n", ctypes.c_size_t), ("signer_id", ctypes.c_void_p),
+                ("signer_slot", ctypes.c_void_p)]
+
+
 # every symbol include/ouro_verify.h (the boundary) and include/ouro_verify_debug.h
 # (diagnostics) declare, with its ctypes signature
 _P = ctypes.c_void_p
@@ -270,6 +291,18 @@ SIGNATURES = {
                                                     _P]),
     "ouro_ledger_views_upload_overlay": (_I, [ctypes.POINTER(LedgerViewsC),
                                               ctypes.POINTER(GenesisDelegsC), ctypes.POINTER(_P)]),
+    "ouro_chain_validate_ledger_pbft_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(EpochNonces),
+              _P, _P, ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip), _P, _P, _P, _P, _P,
+              _P, _P, _P, ctypes.POINTER(ChainTip), ctypes.POINTER(LedgerViewsC),
+              ctypes.POINTER(GenesisDelegsC), ctypes.POINTER(LedgerGlobalsC),
+              ctypes.POINTER(OcertCountersC), _P, _P, _P, _P, ctypes.POINTER(PBftViewsC),
+              ctypes.POINTER(PBftStateC), _P, _P, _P, _P, _P, _P]),
+    "ouro_chain_validate_ledger_pbft_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(EpochNonces),
+              _P, _P, ctypes.POINTER(EnvelopeCfg), ctypes.POINTER(ChainTip), _P, _P, _P, _P, _P,
+              _P, _P, _P, ctypes.POINTER(ChainTip), ctypes.POINTER(LedgerViewsC),
+              ctypes.POINTER(GenesisDelegsC), ctypes.POINTER(LedgerGlobalsC),
+              ctypes.POINTER(OcertCountersC), _P, _P, _P, _P, ctypes.POINTER(PBftViewsC),
+              ctypes.POINTER(PBftStateC), _P, _P, _P, _P, _P, _P]),
     "ouro_chain_validate_ledger_overlay_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64,
                                                      ctypes.c_int64, ctypes.POINTER(EpochNonces),
                                                      _P, _P, ctypes.POINTER(EnvelopeCfg),
@@ -292,6 +325,18 @@ SIGNATURES = {
                                                           ctypes.POINTER(OcertCountersC), _P, _P,
                                                           _P, _P]),
     "ouro_ledger_views_free": (None, [_P]),
+    "ouro_byron_key_hash_batch": (_I, [_SZ, _P, _P]),
+    "ouro_byron_key_hash_batch_host": (_I, [_SZ, _P, _P]),
+    "ouro_byron_key_hash_batch_device": (_I, [_P, _SZ, _P, _P]),
+    "ouro_pbft_window_fold": (_I, [_SZ, _P, _P, ctypes.POINTER(PBftViewsC),
+                                   ctypes.POINTER(PBftStateC), _P, _P, _P, _P, _P]),
+    "ouro_pbft_ledger_checks": (_I, [_SZ, _P, _P, _P, ctypes.POINTER(PBftViewsC),
+                                     ctypes.POINTER(PBftStateC), _P, _P, _P, _P, _P, _P]),
+    "ouro_pbft_ledger_checks_host": (_I, [_SZ, _P, _P, _P, ctypes.POINTER(PBftViewsC),
+                                          ctypes.POINTER(PBftStateC), _P, _P, _P, _P, _P, _P]),
+    "ouro_pbft_views_upload": (_I, [ctypes.POINTER(PBftViewsC), ctypes.POINTER(_P)]),
+    "ouro_pbft_views_free": (None, [_P]),
+    "ouro_pbft_ledger_checks_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),
     "ouro_tpraos_ledger_checks_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P,
                                               ctypes.POINTER(LedgerGlobalsC), _P, _P]),
     "ouro_chain_validate_ledger_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_uint64, ctypes.c_int64,

@@ -161,20 +161,83 @@ int ledger_call(ChainArgs* a, LedgerArgs* g, const LedgerIn& in) {
   return OURO_OK;
 }
 
+// The ledger call above with the Byron ledger-view checks (PBFT.hs:340-357;
+// pbft_view.h) in the same call: RawCall pbft set.
+struct PbftIn {
+  const ouro_pbft_views* views;
+  const ouro_pbft_state* state_in;
+  uint8_t* signer_id_out;
+  uint64_t* signer_slot_out;
+  size_t* n_out;
+  uint8_t* pbft;
+  uint32_t* genesis_row;
+  uint64_t* signed_count;
+};
+struct PbftArgs {
+  RawPbft p{};
+  std::vector<uint32_t> rows;
+  // the window as the call found it (RawPbft state0 points here)
+  std::vector<uint8_t> id0;
+  std::vector<uint64_t> slot0;
+  ~PbftArgs() { pbft_fold_free(p.fold); }
+};
+int pbft_call(ChainArgs* a, PbftArgs* g, const PbftIn& in) {
+  const size_t n = a->c.n;
+  int rc;
+  if ((rc = pbft_views_check(in.views))) return rc;
+  if (in.state_in &&
+      (rc = pbft_state_check(in.state_in, *in.views, in.signer_id_out, in.signer_slot_out, in.n_out)))
+    return rc;
+  if (n && !in.pbft) return fail(OURO_EINVAL, "null pbft");
+  uint32_t* rows = in.genesis_row;
+  try {  // (no exception crosses the C ABI)
+    if (!rows) {
+      g->rows.resize(n);
+      rows = g->rows.data();
+    }
+    if (in.state_in) {
+      const size_t m = in.state_in->n;
+      g->id0.assign(in.state_in->signer_id, in.state_in->signer_id + 28 * m);
+      g->slot0.assign(in.state_in->signer_slot, in.state_in->signer_slot + m);
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(OURO_EDEVICE, "pbft call: out of host memory");
+  }
+  g->p.views = in.views;
+  g->p.pbft = in.pbft;
+  g->p.genesis_row = rows;
+  g->p.signed_count = in.signed_count;
+  if (in.state_in) {
+    g->p.state0 = ouro_pbft_state{in.state_in->n, g->id0.data(), g->slot0.data()};
+    if (!(g->p.fold = pbft_fold_new())) return fail(OURO_EDEVICE, "pbft call: out of host memory");
+    g->p.fold_begin();  // (n = 0 runs no stage: the window passes through)
+  }
+  a->c.pbft = &g->p;
+  return OURO_OK;
+}
+
 // The ouro_chain_* entries, each device / _host pair once: the chain
 // arguments, then the ledger call's, then the validating call's and the
 // spans, then the byron_epoch_slots scan; then the device pipeline or the
 // host path alone.  (n = 0: the tip passes through, nothing is written.)
-int chain_entry(const ChainIn& in, const EnvIn* env, const LedgerIn* ledger, bool host) {
+int chain_entry(const ChainIn& in, const EnvIn* env, const LedgerIn* ledger, bool host,
+                const PbftIn* pbft = nullptr) {
   ChainArgs a;
   RawEnv e{};
   LedgerArgs g;
+  PbftArgs pg;
   if (int rc = chain_call(&a, in)) return rc;
   if (ledger)
     if (int rc = ledger_call(&a, &g, *ledger)) return rc;
+  if (pbft)
+    if (int rc = pbft_call(&a, &pg, *pbft)) return rc;
   if (env)
     if (int rc = validate_call(&a, &e, *env)) return rc;
-  return host ? raw_verify_host(a.c) : raw_verify(a.c);
+  const int rc = host ? raw_verify_host(a.c) : raw_verify(a.c);
+  // the window after the call's last header
+  if (!rc && pbft && pg.p.fold)
+    pbft_fold_end(pg.p.fold, pbft->signer_id_out, pbft->signer_slot_out, pbft->n_out);
+  return rc;
 }
 
 }  // namespace
@@ -305,6 +368,52 @@ int ouro_chain_validate_ledger_overlay_cbor(
                       eta_alpha, leader_alpha, proto, status, verdict, beta_eta, beta_leader,
                       eta_nonce},
                      &e, &l, false);
+}
+
+// the overlay entry with the Byron ledger-view checks (a NULL schedule: the
+// overlay entry itself)
+int ouro_chain_validate_ledger_pbft_cbor(
+    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
+    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
+    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
+    const ouro_genesis_delegs* genesis, const ouro_ledger_globals* globals,
+    const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
+    uint8_t* ledger, uint32_t* pool_row, const ouro_pbft_views* pbft_views,
+    const ouro_pbft_state* pbft_state_in, uint8_t* signer_id_out, uint64_t* signer_slot_out,
+    size_t* n_out, uint8_t* pbft, uint32_t* genesis_row_pbft, uint64_t* signed_count) {
+  const EnvIn e{cfg, tip_in, header_hash, envelope, tip_out};
+  const LedgerIn l{views, genesis, globals, counters, counter_out, present_out, ledger, pool_row};
+  const PbftIn p{pbft_views, pbft_state_in, signer_id_out, signer_slot_out, n_out, pbft,
+                 genesis_row_pbft, signed_count};
+  return chain_entry({raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic, epochs,
+                      eta_alpha, leader_alpha, proto, status, verdict, beta_eta, beta_leader,
+                      eta_nonce},
+                     &e, &l, false, pbft_views ? &p : nullptr);
+}
+
+int ouro_chain_validate_ledger_pbft_cbor_host(
+    const uint8_t* raw, size_t raw_bytes, const uint64_t* off, const uint32_t* len, size_t n,
+    uint64_t slots_per_kes_period, int64_t protocol_magic, const ouro_epoch_nonces* epochs,
+    const uint8_t* eta_alpha, const uint8_t* leader_alpha, const ouro_envelope_cfg* cfg,
+    const ouro_chain_tip* tip_in, uint8_t* proto, uint8_t* status, uint8_t* verdict,
+    uint8_t* beta_eta, uint8_t* beta_leader, uint8_t* eta_nonce, uint8_t* header_hash,
+    uint8_t* envelope, ouro_chain_tip* tip_out, const ouro_ledger_views* views,
+    const ouro_genesis_delegs* genesis, const ouro_ledger_globals* globals,
+    const ouro_ocert_counters* counters, uint64_t* counter_out, uint8_t* present_out,
+    uint8_t* ledger, uint32_t* pool_row, const ouro_pbft_views* pbft_views,
+    const ouro_pbft_state* pbft_state_in, uint8_t* signer_id_out, uint64_t* signer_slot_out,
+    size_t* n_out, uint8_t* pbft, uint32_t* genesis_row_pbft, uint64_t* signed_count) {
+  const EnvIn e{cfg, tip_in, header_hash, envelope, tip_out};
+  const LedgerIn l{views, genesis, globals, counters, counter_out, present_out, ledger, pool_row};
+  const PbftIn p{pbft_views, pbft_state_in, signer_id_out, signer_slot_out, n_out, pbft,
+                 genesis_row_pbft, signed_count};
+  return chain_entry({raw, raw_bytes, off, len, n, slots_per_kes_period, protocol_magic, epochs,
+                      eta_alpha, leader_alpha, proto, status, verdict, beta_eta, beta_leader,
+                      eta_nonce},
+                     &e, &l, true, pbft_views ? &p : nullptr);
 }
 
 int ouro_chain_validate_ledger_cbor(

@@ -14,6 +14,7 @@
 #include "lane_items.h"
 #include "leader.h"
 #include "ledger_view.h"
+#include "pbft_view.h"
 #include "prove.h"
 #include "tpraos.h"
 #include "wide_cores.h"
@@ -345,6 +346,24 @@ void dh_blake2b224_32(const uint8_t* in32, uint8_t* out28) {
   for (int w = 0; w < 16; w++) in[w] = w < 8 ? ld_le32(in32 + 4 * w) : 0u;
   blake2b224_short(o, in, 32);
   for (int k = 0; k < 28; k++) out28[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
+}
+// sha3.h: SHA3-256 of a message of len <= 135 bytes (one block); Byron's
+// hashKey of a 64-byte XPub; pbft_view.h: the OURO_PBFT_* bits of one row
+// (SLOT_OK and WINDOW_OK excepted) and its schedule row
+int dh_sha3_256_short(uint8_t* out32, const uint8_t* msg, uint32_t len) {
+  if (len > 135) return -1;
+  uint8_t blk[136] = {0};
+  if (len) memcpy(blk, msg, len);
+  uint32_t in[34], o[8];
+  for (int w = 0; w < 34; w++) in[w] = ld_le32(blk + 4 * w);
+  sha3_256_short(o, in, len);
+  for (int k = 0; k < 32; k++) out32[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
+  return 0;
+}
+void dh_byron_key_hash(uint8_t* out28, const uint8_t* xpub64) { pbft::key_hash_lane(out28, xpub64); }
+int dh_pbft_check(const ouro_pbft_views* v, const uint8_t* delegate_vk, uint64_t slot,
+                  uint32_t status, uint32_t* genesis_row) {
+  return pbft::pbft_check_lane(*v, delegate_vk, slot, status, genesis_row);
 }
 // lattice.h: (|c0|, c1, sign of c0) for h (32 bytes, < 2^253); returns the bit size
 int dh_half_scalars(const uint8_t* h32, uint8_t* c0, uint8_t* c1, int* c0_neg) {

@@ -62,6 +62,22 @@ int launch_ledger_overlay(hipStream_t st, size_t n, const uint8_t* issuer_vk, co
                           const ouro_ledger_globals& g, const ouro_genesis_delegs& gd,
                           uint8_t* ledger, uint32_t* pool_row);
 
+// the Byron ledger-view checks (kernels_pbft.hip; pbft_view.h): k_pbft_checks
+// over n Byron header rows (delegate_vk n x 64, 4-byte aligned; v: a schedule
+// whose pointers are device pointers) and k_byron_key_hash over n XPubs.  Both
+// cap their grid at launch_ledger's block count (kPbftBlocksMax) and stride over the rest.
+constexpr size_t kPbftBlocksMax = 4096;
+int launch_pbft(hipStream_t st, size_t n, const uint8_t* delegate_vk, const uint64_t* slot,
+                const uint8_t* status, const ouro_pbft_views& v, uint8_t* pbft,
+                uint32_t* genesis_row);
+int launch_byron_key_hash(hipStream_t st, size_t n, const uint8_t* xpub, uint8_t* out);
+// k_pbft_checks_chain: the same rule over a chunk's n PBFT rows in the Byron
+// slicer's arena, the slot of row j read from the envelope record (envelope.h
+// Rec) idx[j] of `rec` (idx null: record j); slot_out[j] receives it
+int launch_pbft_chain(hipStream_t st, size_t n, const uint8_t* delegate_vk, const uint8_t* status,
+                      const void* rec, const uint32_t* idx, const ouro_pbft_views& v,
+                      uint8_t* pbft, uint32_t* genesis_row, uint64_t* slot_out);
+
 // latency mode: eight cores per header (x4 lanes in quad mode), then the
 // finish; n and the option bits read from d_n[0..1].
 // Lanes used <= the kBlock-rounded count lowlat_scratch_words provides for.

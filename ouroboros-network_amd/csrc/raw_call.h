@@ -85,6 +85,46 @@ struct RawLedger {
     if (fold) lv_fold_begin(fold, table0, fold->map, fold->gmap, fold->counter, fold->present);
   }
 };
+// ---- the Byron ledger-view checks (pbft_api.cpp; pbft_view.h) ----
+// the signing-window fold's state (pbft_api.cpp): begin copies the incoming
+// state (null: the empty window), run folds rows in stream order, end writes
+// the window out
+struct PbftFold;
+PbftFold* pbft_fold_new();
+void pbft_fold_free(PbftFold* f);
+void pbft_fold_begin(PbftFold* f, const ouro_pbft_views& v, const ouro_pbft_state* st);
+void pbft_fold_run(PbftFold* f, size_t n, const uint32_t* genesis_row, const uint64_t* slot,
+                   uint8_t* pbft, uint64_t* signed_count);
+void pbft_fold_end(const PbftFold* f, uint8_t* id_out, uint64_t* slot_out, size_t* n_out);
+int pbft_views_check(const ouro_pbft_views* v);
+int pbft_state_check(const ouro_pbft_state* st, const ouro_pbft_views& v, const uint8_t* id_out,
+                     const uint64_t* slot_out, const size_t* n_out);
+int pbft_host_rows(size_t n, const uint8_t* delegate_vk, const uint64_t* slot,
+                   const uint8_t* status, const ouro_pbft_views& v, uint8_t* pbft,
+                   uint32_t* genesis_row);
+// a checked schedule packed and uploaded as one block on `st` (not
+// synchronised; *host must stay alive until the copy has completed)
+int pbft_upload(hipStream_t st, const ouro_pbft_views& v, Buf* buf, std::vector<uint8_t>* host,
+                ouro_pbft_views* d);
+// What ouro_chain_validate_ledger_pbft_cbor adds to a ledger call: the
+// delegation schedule (uploaded once per call behind the ledger views' event:
+// dviews), the fold (begun from state0, the window as the call found it -- a
+// copy, so the caller's outputs may alias it) and the outputs.
+struct RawPbft {
+  const ouro_pbft_views* views;
+  ouro_pbft_views dviews{};
+  std::vector<uint8_t> packed;
+  PbftFold* fold;           // null: no state given
+  ouro_pbft_state state0{};
+  uint8_t* pbft;            // OUT: n
+  uint32_t* genesis_row;    // OUT: n
+  uint64_t* signed_count;   // OUT: n, or null
+  // the fold at state0, where the stage starts: the device pipeline, and again
+  // the host path after a device error.  Idempotent.
+  void fold_begin() {
+    if (fold) pbft_fold_begin(fold, *views, &state0);
+  }
+};
 struct RawCall {
   RawKind kind = kRawHdr;
   const uint8_t* raw = nullptr;
@@ -106,6 +146,7 @@ struct RawCall {
   uint8_t* body_hash = nullptr;  // block kind: OUT, the computed bbHash (n x 32), or null
   RawEnv* env = nullptr;         // chain kind: also the header envelope (validate), or null
   RawLedger* ledger = nullptr;   // chain kind: also the ledger-view checks, or null
+  RawPbft* pbft = nullptr;       // a ledger call: also the Byron ledger-view checks, or null
   // every span was checked by the entry (between its other argument checks):
   // raw_verify / raw_verify_host do not walk them again
   bool spans_checked = false;

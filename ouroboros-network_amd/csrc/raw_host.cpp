@@ -90,6 +90,61 @@ int raw_host_ledger(const RawCall& c) {
   return OURO_OK;
 }
 
+// a PBFT call on the host path: the Byron headers sliced again on the host in
+// chunks (their slots from the envelope's record of the same header),
+// pbft_check_lane over their rows, the window fold in stream order restarted
+// from the state as the call found it (c.proto is the chain kind's, already
+// written)
+int raw_host_pbft(const RawCall& c) {
+  RawPbft& B = *c.pbft;
+  B.fold_begin();
+  const size_t C = 1 << 16;
+  std::vector<uint32_t> ix, rows;
+  std::vector<uint64_t> off, slots;
+  std::vector<uint32_t> len;
+  std::vector<uint8_t> st, bits, arena;
+  for (size_t lo = 0; lo < c.n; lo += C) {
+    const size_t m = std::min(C, c.n - lo);
+    memset(B.pbft + lo, 0, m);
+    if (B.signed_count) memset(B.signed_count + lo, 0, 8 * m);
+    ix.clear();
+    for (size_t i = lo; i < lo + m; i++) {
+      B.genesis_row[i] = OURO_LV_NO_POOL;
+      if (c.proto[i] == OURO_PROTO_PBFT) ix.push_back((uint32_t)(i - lo));
+    }
+    const size_t q = ix.size();
+    if (!q) continue;
+    off.resize(q), len.resize(q), slots.resize(q), st.resize(q), bits.resize(q), rows.resize(q);
+    for (size_t j = 0; j < q; j++) {
+      off[j] = c.off[lo + ix[j]];
+      len[j] = c.len[lo + ix[j]];
+      env::Rec r;
+      env::rec_clear(&r);
+      cbor::byron_pack_one<false>(c.raw, off[j], len[j], -1, cbor::ByronOut{}, j, &r,
+                                  c.env->cfg.byron_epoch_slots);
+      slots[j] = r.slot;
+    }
+    arena.resize(ouro_byron_pack_bytes(q, len.data()));
+    ouro_byron_batch b;
+    int rc = ouro_byron_pack_cbor(c.raw, c.raw_bytes, off.data(), len.data(), q, c.magic,
+                                  arena.data(), arena.size(), &b, st.data(), 0);
+    if (rc) return fail(rc, "ouro_byron_pack_cbor: bad arguments");
+    if ((rc = pbft_host_rows(q, b.delegate_vk, slots.data(), st.data(), *B.views, bits.data(),
+                             rows.data())))
+      return rc;
+    for (size_t j = 0; j < q; j++) {
+      if (st[j] != OURO_PACK_OK && st[j] != OURO_PACK_EBB) continue;
+      const size_t i = lo + ix[j];
+      B.pbft[i] = bits[j];
+      B.genesis_row[i] = rows[j];
+      if (B.fold)
+        pbft_fold_run(B.fold, 1, &rows[j], &slots[j], &B.pbft[i],
+                      B.signed_count ? &B.signed_count[i] : nullptr);
+    }
+  }
+  return OURO_OK;
+}
+
 // The combined entry on the host path: per chunk of 64 K headers the same
 // partition as a mixed device chunk -- each class's offset / length (and
 // alpha) list through its own host slicer and verification, both result sets
@@ -168,6 +223,8 @@ int raw_host(const RawCall& c) {
       if (int rc = raw_host_chain(c)) return rc;
       if (c.ledger)
         if (int rc = raw_host_ledger(c)) return rc;
+      if (c.pbft)
+        if (int rc = raw_host_pbft(c)) return rc;
       if (!c.env) return OURO_OK;
       // a validating call: the envelope with the host build of the same routines
       if (int rc = env_host_run(c.raw, c.off, c.len, c.n, c.env->cfg, c.env->tip, nullptr,

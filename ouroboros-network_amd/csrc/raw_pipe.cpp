@@ -157,6 +157,22 @@ RawLvOut raw_lv_out(size_t mt) {
   return l;
 }
 
+// a PBFT call's block of a chunk's mb PBFT rows: bits | schedule rows | slots,
+// on the device (where a mixed chunk's index list follows) and in pinned memory
+struct RawPbOut {
+  size_t bits, rows, slot, back, idx, total;
+};
+RawPbOut raw_pb_out(size_t mb) {
+  RawPbOut l;
+  l.bits = 0;
+  l.rows = a16(mb);
+  l.slot = l.rows + a16(4 * mb);
+  l.back = l.slot + 8 * mb;
+  l.idx = a16(l.back);
+  l.total = l.idx + a16(4 * mb);
+  return l;
+}
+
 // a raw-CBOR knob (knobs.h; 0 = unset) if inside [lo, hi], else the default
 size_t knob_size(const std::atomic<size_t>& k, size_t dflt, size_t lo, size_t hi) {
   const size_t v = k.load(std::memory_order_relaxed);
@@ -396,6 +412,30 @@ void raw_drain_ledger(const RawSlot& s, const RawCall& c, size_t mt, const uint3
   }
 }
 
+// a drained chunk's PBFT results into the caller's order, then the window fold
+// over them in that order (idx: a mixed chunk's PBFT rows' indices, ascending,
+// or null: row j is header j); status: the Byron slicer's, per row
+void raw_drain_pbft(const RawSlot& s, const RawCall& c, size_t mb, const uint32_t* idx,
+                    const uint8_t* status) {
+  RawPbft& B = *c.pbft;
+  memset(B.pbft + s.lo, 0, s.m);
+  for (size_t i = 0; i < s.m; i++) B.genesis_row[s.lo + i] = OURO_LV_NO_POOL;
+  if (B.signed_count) memset(B.signed_count + s.lo, 0, 8 * s.m);
+  const RawPbOut PO = raw_pb_out(mb);
+  const uint8_t* bits = s.h_pb + PO.bits;
+  const uint32_t* rows = reinterpret_cast<const uint32_t*>(s.h_pb + PO.rows);
+  const uint64_t* slot = reinterpret_cast<const uint64_t*>(s.h_pb + PO.slot);
+  for (size_t j = 0; j < mb; j++) {
+    if (status[j] != OURO_PACK_OK && status[j] != OURO_PACK_EBB) continue;
+    const size_t i = s.lo + (idx ? idx[j] : j);
+    B.pbft[i] = bits[j];
+    B.genesis_row[i] = rows[j];
+    if (B.fold)
+      pbft_fold_run(B.fold, 1, &rows[j], &slot[j], &B.pbft[i],
+                    B.signed_count ? &B.signed_count[i] : nullptr);
+  }
+}
+
 // the slot's stream: upload, device slicer(s), kernel(s), results back
 int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
   const bool alphas = c.ea != nullptr;
@@ -467,6 +507,33 @@ int raw_launch(RawSlot& s, const RawCall& c, const RawChunk& k) {
                               reinterpret_cast<env::Rec*>(de + EO.ends))))
       return rc;
     OURO_HIP(hipMemcpyAsync(s.h_env, de + EO.hash, EO.back, hipMemcpyDeviceToHost, s.st));
+    // the Byron ledger-view checks behind the Byron slicer and the envelope
+    // slicer, on the same stream: the rows' delegate keys and statuses lie in
+    // the slot's arena and result block, their slots in the envelope records
+    // (a mixed chunk's through the index list of its PBFT rows)
+    if (c.pbft && mb) {
+      const RawPbOut PO = raw_pb_out(mb);
+      if ((rc = ensure(s.d_pb, PO.total)) || (rc = pinned_at_least(&s.h_pb, &s.h_pb_cap, PO.back)))
+        return rc;
+      uint8_t* dpb = static_cast<uint8_t*>(s.d_pb.p);
+      const bool mixed = s.mode == kModeMixed;
+      uint8_t* barena = cbor::arena_base(mixed ? darena + arena_t : darena);
+      const cbor::ByronOut bo = cbor::byron_arena_out(barena, bl);
+      const uint8_t* bstatus = mixed ? dout + a16(O.total) : dout + O.status;
+      const uint32_t* didx = nullptr;
+      if (mixed) {
+        OURO_HIP(hipMemcpyAsync(dpb + PO.idx, s.idx.data() + mt, 4 * mb, hipMemcpyHostToDevice,
+                                s.st));
+        didx = reinterpret_cast<const uint32_t*>(dpb + PO.idx);
+      }
+      OURO_HIP(hipStreamWaitEvent(s.st, c.ledger->uploaded, 0));
+      if ((rc = launch_pbft_chain(s.st, mb, bo.delegate_vk, bstatus, de + EO.rec, didx,
+                                  c.pbft->dviews, dpb + PO.bits,
+                                  reinterpret_cast<uint32_t*>(dpb + PO.rows),
+                                  reinterpret_cast<uint64_t*>(dpb + PO.slot))))
+        return rc;
+      OURO_HIP(hipMemcpyAsync(s.h_pb, dpb, PO.back, hipMemcpyDeviceToHost, s.st));
+    }
   }
   OURO_HIP(hipMemcpyAsync(s.h_out, dout, back, hipMemcpyDeviceToHost, s.st));
   if (back_b)
@@ -515,6 +582,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
       if (c.nonce) memcpy(c.nonce + 32 * i, h + O.nonce + 32 * j, 32);
     }
     const uint8_t* hb = s.h_out + a16(raw_out_bytes(c, O, mt));
+    if (c.pbft) raw_drain_pbft(s, c, mb, s.idx.data() + mt, hb + OB.status);
     for (size_t j = 0; j < mb; j++) {
       const size_t i = s.lo + s.idx[mt + j];
       const uint8_t st = hb[OB.status + j];
@@ -536,6 +604,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
     for (size_t i = 0; i < s.m; i++)
       c.verdict[s.lo + i] = st[i] == OURO_PACK_EBB ? 1 : (st[i] == OURO_PACK_OK && v[i] ? 1 : 0);
     if (c.ledger) raw_drain_ledger(s, c, 0, nullptr, st);
+    if (c.pbft) raw_drain_pbft(s, c, s.m, nullptr, st);
     if (hdr) {  // the combined entry: a PBFT header has no VRF outputs
       if (c.be) memset(c.be + 64 * s.lo, 0, 64 * s.m);
       if (c.bl) memset(c.bl + 64 * s.lo, 0, 64 * s.m);
@@ -548,6 +617,7 @@ int raw_drain(RawSlot& s, const RawCall& c) {
   for (size_t i = 0; i < s.m; i++) c.verdict[s.lo + i] = st[i] == OURO_PACK_OK ? v[i] : 0;
   if (c.kind == kRawBlock && c.body_hash) memcpy(c.body_hash + 32 * s.lo, s.h_out + O.be, 32 * s.m);
   if (c.ledger) raw_drain_ledger(s, c, s.m, nullptr, st);
+  if (c.pbft) raw_drain_pbft(s, c, 0, nullptr, st);
   if (hdr) {
     if (c.be) memcpy(c.be + 64 * s.lo, s.h_out + O.be, 64 * s.m);
     if (c.bl) memcpy(c.bl + 64 * s.lo, s.h_out + O.bl, 64 * s.m);
@@ -589,6 +659,13 @@ int raw_run(const RawCall& c, const std::vector<RawChunk>& chunks) {
     if ((rc = lv_upload(p.s[0].st, *c.ledger->views, c.ledger->genesis, &p.d_views,
                         &c.ledger->packed, &c.ledger->dviews, &c.ledger->dgenesis)))
       return rc;
+    // (the delegation schedule of a PBFT call on the same stream, before the event)
+    if (c.pbft) {
+      c.pbft->fold_begin();
+      if ((rc = pbft_upload(p.s[0].st, *c.pbft->views, &p.d_pviews, &c.pbft->packed,
+                            &c.pbft->dviews)))
+        return rc;
+    }
     OURO_HIP(hipEventRecord(p.views_up, p.s[0].st));
     c.ledger->uploaded = p.views_up;
   }

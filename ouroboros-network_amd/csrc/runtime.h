@@ -129,6 +129,12 @@ struct RawSlot {
   Buf d_lv;
   uint8_t* h_lv = nullptr;
   size_t h_lv_cap = 0;
+  // the Byron ledger-view checks of a call with RawCall pbft: bits | rows |
+  // slots of the chunk's PBFT rows (and a mixed chunk's index list) on the
+  // device; bits | rows | slots in pinned memory
+  Buf d_pb;
+  uint8_t* h_pb = nullptr;
+  size_t h_pb_cap = 0;
   size_t lo = 0, m = 0;
   bool busy = false;
   // the combined entry (kRawChain): the chunk's era make-up and, for a mixed
@@ -144,6 +150,7 @@ struct RawPipe {
   RawSlot s[kRawMaxSlots];
   Buf d_views;  // a call's packed ledger views (RawLedger), uploaded once per call
   hipEvent_t views_up = nullptr;
+  Buf d_pviews;  // a call's packed delegation schedule (RawPbft), likewise
 };
 
 // Everything a calling thread needs on one device: its stream, the scratch

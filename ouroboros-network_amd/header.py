@@ -706,7 +706,7 @@ def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_
                                epochs: Optional[EpochNonces] = None,
                                eta_alpha: Optional[np.ndarray] = None,
                                leader_alpha: Optional[np.ndarray] = None, nonce: bool = False,
-                               host: bool = False):
+                               host: bool = False, pbft=None, pbft_state=None):
     """validate_chain_cbor with the ledger-view checks in the same call
     (include/ouro_verify.h ouro_chain_validate_ledger_cbor): `views` (a
     ledger.LedgerViews), `globals_` (a ledger.Globals) and optionally the OCERT
@@ -716,7 +716,14 @@ def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_
     there.  Returns
     validate_chain_cbor's tuple and then (ledger, pool_row, counters_after):
     the LV_* bits (0 for a PBFT or unsliced header), each issuer's view row,
-    and the table after the fold (None without counters)."""
+    and the table after the fold (None without counters).  With `pbft` (a
+    pbft.PBftViews; ouro_chain_validate_ledger_pbft_cbor) the Byron ledger-view
+    checks run in the same call, with `pbft_state` (a pbft.PBftState) the
+    window fold too, and the tuple goes on with (pbft, genesis_row,
+    signed_count, state_after): the PBFT_* bits (0 for a TPraos or unsliced
+    header), each delegate's schedule row, the fold's counts and the window
+    afterwards (None without a state).  pbft=False calls that entry with a NULL
+    schedule -- the overlay entry, byte for byte -- and returns the plain tuple."""
     import ctypes
 
     from . import _native
@@ -752,18 +759,38 @@ def validate_chain_ledger_cbor(raw_headers, slots_per_kes_period: int, protocol_
         name = "ouro_chain_validate_ledger_overlay_cbor" + ("_host" if host else "")
         c_gen = genesis.c_struct()
         gen = (ctypes.byref(c_gen),)
+    tail = ()
+    if pbft is not None:
+        from . import pbft as PB
+
+        name = "ouro_chain_validate_ledger_pbft_cbor" + ("_host" if host else "")
+        if genesis is None:
+            gen = (None,)
+        pb_bits, pb_rows, pb_cnt = np.zeros(m, np.uint8), np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        if pbft is False:   # the entry with a NULL schedule: the overlay entry
+            tail = (None,) * 5 + (ptr(pb_bits), ptr(pb_rows), ptr(pb_cnt))
+        else:
+            c_pv = pbft.c_struct()
+            c_ps, id_out, slot_out, n_out, _keep = PB._state_args(pbft_state, pbft.window)
+            tail = (ctypes.byref(c_pv), None if c_ps is None else ctypes.byref(c_ps), ptr(id_out),
+                    ptr(slot_out), None if c_ps is None else ctypes.addressof(n_out),
+                    ptr(pb_bits), ptr(pb_rows), ptr(pb_cnt))
     rc = getattr(lib, name)(ptr(buf), buf.size, ptr(off), ptr(ln), n, slots_per_kes_period,
                             protocol_magic, e, ptr(ea), ptr(la), ctypes.byref(c_cfg),
                             ctypes.byref(t_in), ptr(proto), ptr(status), ptr(verdict), ptr(be),
                             ptr(bl), ptr(en), ptr(hh), ptr(bits), ctypes.byref(t_out),
                             ctypes.byref(cv), *gen, ctypes.byref(cg),
                             None if cc is None else ctypes.byref(cc), ptr(co), ptr(po),
-                            ptr(ledger), ptr(rows))
+                            ptr(ledger), ptr(rows), *tail)
     _native.check(rc, name)
     crypto = (proto[:n], status[:n], verdict[:n], be[:n], bl[:n])
     if nonce:
         crypto += (en[:n],)
     valid = np.where(proto[:n] == PROTO_PBFT, verdict[:n] == 1, (verdict[:n] & 0x0F) == 0x0F)
     after = None if counters is None else counters.after(co, po)
-    return (crypto, hh[:n], bits[:n], _py_tip(t_out), E.first_invalid(bits[:n], valid),
-            ledger[:n], rows[:n], after)
+    out = (crypto, hh[:n], bits[:n], _py_tip(t_out), E.first_invalid(bits[:n], valid),
+           ledger[:n], rows[:n], after)
+    if pbft is not None and pbft is not False:
+        out += (pb_bits[:n], pb_rows[:n], pb_cnt[:n],
+                None if pbft_state is None else PB._state_after(id_out, slot_out, n_out))
+    return out
