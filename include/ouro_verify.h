@@ -376,10 +376,13 @@ int ouro_tpraos_verify_batch_epochs(const ouro_tpraos_batch *b, const ouro_epoch
 #define OURO_PACK_ESIZE 3u  /* a fixed-size crypto field has the wrong length  */
 #define OURO_PACK_EBYRON 4u /* HFC era 0: a Byron header, not TPraos          */
 #define OURO_PACK_ESPAN 5u  /* (device slicer) span outside raw_bytes          */
-#define OURO_PACK_EBB 6u    /* (Byron slicer) an epoch-boundary header: PBFT
-                               checks no signature on it (PBFT.hs:327-328)     */
-#define OURO_PACK_ESHELLEY 7u /* (Byron slicer) HFC era >= 1: not a Byron header */
-#define OURO_PACK_ECAP 8u   /* (witness slicer) the block's rows pass a capacity */
+#define OURO_PACK_EBB 6u    /* (Byron slicers) an epoch-boundary header: PBFT
+                               checks no signature on it (PBFT.hs:327-328);
+                               an epoch-boundary block (HFC block tag 0)       */
+#define OURO_PACK_ESHELLEY 7u /* (Byron slicers) HFC era >= 1: not a Byron header;
+                                 HFC block tag >= 2: not a Byron block          */
+#define OURO_PACK_ECAP 8u   /* (witness slicer, Byron block _device entry) the
+                               block's rows pass a capacity                    */
 size_t ouro_tpraos_pack_bytes(size_t n);
 int ouro_tpraos_pack_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
                           const uint32_t *len, size_t n, uint64_t slots_per_kes_period,
@@ -537,7 +540,8 @@ int ouro_blake2b256_batch_device(void *stream, size_t n, const uint8_t *msg, siz
  *     see ouro_blake2b256_batch_device; arena of
  *     ouro_block_pack_bytes(n) bytes), enqueued on `stream`, not synchronised;
  *     a span outside raw_bytes is per-block status OURO_PACK_ESPAN.
- * Out of scope: _multi forms, Byron blocks, the latency plans. */
+ * Out of scope: _multi forms, the latency plans.  Byron blocks (their body
+ * proof and block signature): ouro_byron_block_integrity_verify_cbor below. */
 #define OURO_BLK_KES_OK 0x01u  /* verifyHeaderIntegrity                       */
 #define OURO_BLK_BODY_OK 0x02u /* blockMatchesHeader: bbHash == bodyHash      */
 #define OURO_BLK_ALL_OK 0x03u  /* verifyBlockIntegrity; test with the mask    */
@@ -685,6 +689,107 @@ int ouro_byron_pack_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *o
 int ouro_byron_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
                            const uint32_t *len, size_t n, int64_t protocol_magic,
                            uint8_t *status, uint8_t *verdict);
+/* Byron whole-block storage integrity straight from raw block CBOR: replaces
+ * verifyBlockIntegrity cfg blk = verifyHeaderIntegrity cfg hdr &&
+ * blockMatchesHeader hdr blk (ouroboros-consensus-byron/src/Ouroboros/
+ * Consensus/Byron/Ledger/Integrity.hs:63-68) for the callers listed at
+ * ouro_block_integrity_verify_cbor, over the Byron prefix of a Cardano chain.
+ * Block i is raw[off[i] .. off[i] + len[i]) in either form
+ *   [tag, block]                        on disk (Byron-only and Cardano alike)
+ *   #6.24(bytes .cbor [tag, block])     on the wire
+ * tag 0 = EBB (status OURO_PACK_EBB, verdict OURO_BYB_ALL_OK, zero tx_root: the
+ * reference checks nothing of an EBB; it must end where its span ends), 1 =
+ * regular, 2 and up = Shelley family (OURO_PACK_ESHELLEY, verdict 0).
+ *   regular = [header, body, extra]           a definite array(3), ending at its span
+ *   header  = [magic, prevHash, proof, consensusData, extraData], as
+ *             ouro_byron_pack_cbor reads it after unwrapping
+ *   proof   = [[txpNumber, txpRoot, txpWitnessesHash], [sscTag, sscHash],
+ *              dlgHash, updHash]
+ *   body    = [txPayload, sscPayload, dlgPayload, updPayload]   definite array(4)
+ *   txPayload = [* [tx, witnesses]]   definite or indefinite; each element a
+ *               definite array(2) of two arrays, recorded as they stand
+ * verifyHeaderIntegrity (OURO_BYB_HDR_OK): the block signature under ByronDSIGN
+ * over the message of ouro_byron_pack_cbor built with protocol_magic, and the
+ * header's own magic field == protocol_magic (Integrity.hs:46-56);
+ * protocol_magic = -1: each header's own field for both.
+ * blockMatchesHeader (OURO_BYB_BODY_OK; CC.abobMatchesBody, Byron/Ledger/
+ * Block.hs:167-168) = the five bits below, every hash Blake2b-256 over bytes as
+ * they stand in the block:
+ *   TXNUM   txpNumber == the number n of transactions
+ *   TXROOT  txpRoot == the Merkle root: leaf_k = H(0x00 || tx_k), node(l, r) =
+ *           H(0x01 || l || r); H("") for n = 0, the leaf for n = 1, else
+ *           node(root(first i), root(rest)), i the largest power of two < n
+ *   TXWIT   txpWitnessesHash == H(0x9f || witnesses_0 || ... || 0xff)
+ *   DLG     dlgHash == H(dlgPayload)        UPD  updHash == H(updPayload)
+ * The SSC proof is not compared (the reference's SscProof is a unit); only
+ * [uint, bytes(32)] is demanded of it.
+ * Pinned by the reference's golden Byron block: the leaf form, the witnesses
+ * list form, the two payload hashes.  NOT pinned by any reference fixture
+ * (restated from cardano-ledger's Byron part, outside the reference tree): the
+ * tree shape for n >= 2 and the empty root; non-canonical or indefinite
+ * encodings inside a witness vector (the reference may re-serialise there;
+ * this library hashes the bytes as they stand); that the SSC proof's content
+ * is ignored.  Byron transaction witnesses are not verified.
+ * Outputs: status[i] = OURO_PACK_* (OK, ECBOR, ESHAPE, ESIZE, EBB, ESHELLEY;
+ * ESPAN and ECAP from the _device form); verdict[i] = OURO_BYB_* bits, 0 for a
+ * block that does not slice; tx_root (n x 32, may be NULL) the computed Merkle
+ * root, zeros unless the status is OURO_PACK_OK.
+ *   ouro_byron_block_count_cbor[_host]: the slicer's count pass alone: status,
+ *     ntx[i], gather_bytes[i] (the block's witness vectors + 2) and
+ *     msg_bytes[i] (its signed message), zeros unless the status is
+ *     OURO_PACK_OK, and totals[0..2] their sums -- what a caller of the _device
+ *     form sizes the three capacities from.
+ *   ouro_byron_block_integrity_verify_cbor: host buffers, synchronous, on the
+ *     calling thread's stream, in consecutive groups of whole blocks under a
+ *     byte budget (OURO_BYRON_BLOCK_GROUP_BYTES), each sized from its count
+ *     pass; a device error recomputes the call on the host path.
+ *   ouro_byron_block_integrity_verify_cbor_host: the host path alone.
+ *   All four return OURO_EINVAL, before any work, for NULLs, a span outside
+ *   raw_bytes, or a protocol_magic outside -1 .. 2^32 - 1.
+ *   ouro_byron_block_integrity_verify_cbor_device: device pointers (raw as for
+ *     ouro_blake2b256_batch_device; off 8-byte, len 4-byte, tx_root 16-byte
+ *     aligned; work of ouro_byron_block_work_bytes(n, tx_cap, gather_cap,
+ *     msg_cap) bytes), enqueued on `stream`, not synchronised, no host round
+ *     trip.  A span outside raw_bytes is per-block status OURO_PACK_ESPAN.  A
+ *     regular block whose transaction rows, gathered bytes or message would
+ *     pass a capacity writes nothing and has status OURO_PACK_ECAP, verdict 0;
+ *     the blocks that fit are a prefix of the regular ones.
+ * Out of scope: one entry for mixed eras (partition a stream by the block tag),
+ * _multi forms, the chunked raw pipeline, Byron transaction witnesses, the
+ * latency plans. */
+#define OURO_BYB_HDR_OK 0x01u    /* verifyHeaderIntegrity                 */
+#define OURO_BYB_BODY_OK 0x02u   /* blockMatchesHeader: all five below    */
+#define OURO_BYB_TXNUM_OK 0x04u
+#define OURO_BYB_TXROOT_OK 0x08u
+#define OURO_BYB_TXWIT_OK 0x10u
+#define OURO_BYB_DLG_OK 0x20u
+#define OURO_BYB_UPD_OK 0x40u
+#define OURO_BYB_ALL_OK 0x7fu
+int ouro_byron_block_count_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                const uint32_t *len, size_t n, int64_t protocol_magic,
+                                uint8_t *status, uint32_t *ntx, uint32_t *gather_bytes,
+                                uint32_t *msg_bytes, uint64_t *totals);
+int ouro_byron_block_count_cbor_host(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                     const uint32_t *len, size_t n, int64_t protocol_magic,
+                                     uint8_t *status, uint32_t *ntx, uint32_t *gather_bytes,
+                                     uint32_t *msg_bytes, uint64_t *totals);
+int ouro_byron_block_integrity_verify_cbor(const uint8_t *raw, size_t raw_bytes,
+                                           const uint64_t *off, const uint32_t *len, size_t n,
+                                           int64_t protocol_magic, uint8_t *status,
+                                           uint8_t *verdict, uint8_t *tx_root);
+int ouro_byron_block_integrity_verify_cbor_host(const uint8_t *raw, size_t raw_bytes,
+                                                const uint64_t *off, const uint32_t *len,
+                                                size_t n, int64_t protocol_magic,
+                                                uint8_t *status, uint8_t *verdict,
+                                                uint8_t *tx_root);
+size_t ouro_byron_block_work_bytes(size_t n, size_t tx_cap, size_t gather_cap, size_t msg_cap);
+int ouro_byron_block_integrity_verify_cbor_device(void *stream, const uint8_t *raw,
+                                                  size_t raw_bytes, const uint64_t *off,
+                                                  const uint32_t *len, size_t n,
+                                                  int64_t protocol_magic, size_t tx_cap,
+                                                  size_t gather_cap, size_t msg_cap, void *work,
+                                                  size_t work_bytes, uint8_t *status,
+                                                  uint8_t *verdict, uint8_t *tx_root);
 /* A raw header stream across eras and epochs in ONE call: what ChainDB's
  * re-validation of a stored suffix (LgrDB.hs:350-368), ImmutableDB /
  * VolatileDB replay and ChainSync windows of a Cardano chain actually hold --

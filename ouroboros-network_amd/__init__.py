@@ -9,6 +9,7 @@ is the gfx950 library ``lib/libouro_verify.so`` behind the C ABI in
 from . import _native
 from ._native import DeviceError, NativeUnavailable
 from .block import blake2b256_batch, parse_block, verify_block_integrity_cbor
+from .byron_block import count_byron_blocks, parse_byron_block, verify_byron_block_integrity
 from .byron import (ByronDSIGN, dlg_cert_message, pack_byron_cbor, parse_byron_header,
                     verify_byron_cbor, verify_byron_headers, verify_delegation_certs)
 from .dsign import Ed25519DSIGN
@@ -44,6 +45,7 @@ __all__ = [
     "byron_key_hash",
     "chain_envelope_cbor",
     "count_block_witnesses",
+    "count_byron_blocks",
     "counter_fold",
     "first_invalid",
     "kes_period",
@@ -53,6 +55,7 @@ __all__ = [
     "dlg_cert_message",
     "pack_byron_cbor",
     "parse_block",
+    "parse_byron_block",
     "parse_byron_header",
     "parse_witnesses",
     "pbft_checks",
@@ -63,6 +66,7 @@ __all__ = [
     "validate_chain_pbft_cbor",
     "verify_block_integrity_cbor",
     "verify_block_witnesses",
+    "verify_byron_block_integrity",
     "verify_byron_cbor",
     "verify_byron_headers",
     "verify_chain_cbor",

@@ -113,6 +113,73 @@ OURO_HD inline void byron_env(const Cur& c, uint64_t base, uint64_t h, bool ebb,
   er->hdr_len = (uint32_t)(c.n - h);
 }
 
+// The regular header whose plain array(5) item starts at index h of `c`: its
+// fields, the signed message and row i of `o`, and the optional envelope
+// record.  Shared by the header slicer (byron_pack_one, after it has unwrapped
+// the wire form) and the block slicer (cbor_byron_block.h, item 0 of a regular
+// block); `c` bounds every read.  must_end: where the item has to end (kAnyEnd:
+// anywhere); *end receives its end, proof[0..1] the span of field 2 (the body
+// proof), *msg_bytes the length of the signed message -- each optional.
+// kRows = false: the acceptance, `er` and those three alone.
+template <bool kRows = true>
+OURO_HD inline uint8_t byron_fields(const Cur& c, uint64_t h, uint64_t base, int64_t magic_cfg,
+                                    const ByronOut& o, size_t i, env::Rec* er, uint64_t epoch_slots,
+                                    uint64_t must_end, uint64_t* end = nullptr,
+                                    uint64_t* proof = nullptr, uint32_t* msg_bytes = nullptr) {
+  uint8_t st;
+  uint64_t fs[5], fe[5], cs[4], ce[4], bs[2], be[2], is[2], ie[2], ds[4], de[4];
+  // one walk of the header's five fields; it must end where the payload does
+  if ((st = fixed_array(c, h, fs, fe, 5))) return st;
+  if (must_end != kAnyEnd && fe[4] != must_end) return OURO_PACK_ECBOR;  // trailing bytes in CBOR-in-CBOR
+  uint64_t magic;
+  if (!uint_le(c, fs[0], kWord32Max, &magic)) return OURO_PACK_ESHAPE;
+  if ((st = fixed_array(c, fs[3], cs, ce, 4))) return st;
+  if ((st = fixed_array(c, cs[3], bs, be, 2))) return st;
+  uint64_t sigkind;
+  if (!uint_at(c, bs[0], &sigkind) || sigkind != 2) return OURO_PACK_ESHAPE;
+  if ((st = fixed_array(c, bs[1], is, ie, 2))) return st;
+  if ((st = fixed_array(c, is[0], ds, de, 4))) return st;
+  const uint8_t *gvk, *dvk, *sg;
+  const int r0 = bytes_at(c, ds[1], 64, &gvk), r1 = bytes_at(c, ds[2], 64, &dvk),
+            r2 = bytes_at(c, is[1], 64, &sg);
+  if (r0 == kBytesShape || r1 == kBytesShape || r2 == kBytesShape) return OURO_PACK_ESHAPE;
+  if (r0 | r1 | r2) return OURO_PACK_ESIZE;
+  if (er) byron_env(c, base, h, false, fs[1], cs[0], cs[2], epoch_slots, er);
+  if (end) *end = fe[4];
+  if (proof) {
+    proof[0] = fs[2];
+    proof[1] = fe[2];
+  }
+  const uint64_t m = magic_cfg < 0 ? magic : (uint64_t)magic_cfg;
+  if (msg_bytes) {  // "01", the XPub, 0x09, CBOR(magic), 0x85, the five spans
+    uint8_t mh[9];
+    *msg_bytes = (uint32_t)(2 + 64 + 1 + (uint64_t)put_uint(mh, m) + 1 + (fe[1] - fs[1]) +
+                            (fe[2] - fs[2]) + (ce[0] - cs[0]) + (ce[2] - cs[2]) + (fe[4] - fs[4]));
+  }
+  if (!kRows) return OURO_PACK_OK;
+  uint8_t* d = o.msg + o.msg_off[i];
+  uint64_t n = 0;
+  d[n++] = '0';
+  d[n++] = '1';
+  n += put_span(d + n, c, (uint64_t)(gvk - c.b), (uint64_t)(gvk - c.b) + 64);
+  d[n++] = 0x09;
+  n += (uint64_t)put_uint(d + n, m);
+  d[n++] = 0x85;  // ToSign: encodeListLen 5
+  n += put_span(d + n, c, fs[1], fe[1]);  // prevHash
+  n += put_span(d + n, c, fs[2], fe[2]);  // bodyProof
+  n += put_span(d + n, c, cs[0], ce[0]);  // slotId
+  n += put_span(d + n, c, cs[2], ce[2]);  // difficulty
+  n += put_span(d + n, c, fs[4], fe[4]);  // extraData
+  o.msg_len[i] = (uint32_t)n;
+  const uint64_t g0 = (uint64_t)(gvk - c.b), d0 = (uint64_t)(dvk - c.b), s0 = (uint64_t)(sg - c.b);
+  put_span(o.pk + 32 * i, c, d0, d0 + 32);
+  put_span(o.sig + 64 * i, c, s0, s0 + 64);
+  put_span(o.genesis_vk + 64 * i, c, g0, g0 + 64);
+  put_span(o.delegate_vk + 64 * i, c, d0, d0 + 64);
+  o.magic[i] = magic;
+  return OURO_PACK_OK;
+}
+
 // magic_cfg: the configured ProtocolMagicId, or -1 for each header's own
 // er (optional): the header's envelope record, for a regular header and for
 // an epoch-boundary one (whose fields only this looks at); epoch_slots: the
@@ -162,9 +229,8 @@ OURO_HD inline uint8_t byron_pack_one(const uint8_t* raw, uint64_t base, uint32_
     if (!uint_le(c, s2[0], ~0ull, &kind) || kind > 1) return OURO_PACK_ESHAPE;
     h = s2[1];
   }
-  uint64_t fs[5], fe[5], cs[4], ce[4], bs[2], be[2], is[2], ie[2], ds[4], de[4];
   if (kind == 0) {  // no signature; its fields are not checked
-    uint64_t he;
+    uint64_t he, fs[5], fe[5], bs[2], be[2];
     if (!skip(c, h, &he)) return OURO_PACK_ECBOR;
     if (he != c.n) return OURO_PACK_ECBOR;
     if (er) {
@@ -175,46 +241,7 @@ OURO_HD inline uint8_t byron_pack_one(const uint8_t* raw, uint64_t base, uint32_
     }
     return OURO_PACK_EBB;
   }
-  // one walk of the header's five fields; it must end where the payload does
-  if ((st = fixed_array(c, h, fs, fe, 5))) return st;
-  if (fe[4] != c.n) return OURO_PACK_ECBOR;  // trailing bytes in CBOR-in-CBOR
-  uint64_t magic;
-  if (!uint_le(c, fs[0], kWord32Max, &magic)) return OURO_PACK_ESHAPE;
-  if ((st = fixed_array(c, fs[3], cs, ce, 4))) return st;
-  if ((st = fixed_array(c, cs[3], bs, be, 2))) return st;
-  uint64_t sigkind;
-  if (!uint_at(c, bs[0], &sigkind) || sigkind != 2) return OURO_PACK_ESHAPE;
-  if ((st = fixed_array(c, bs[1], is, ie, 2))) return st;
-  if ((st = fixed_array(c, is[0], ds, de, 4))) return st;
-  const uint8_t *gvk, *dvk, *sg;
-  const int r0 = bytes_at(c, ds[1], 64, &gvk), r1 = bytes_at(c, ds[2], 64, &dvk),
-            r2 = bytes_at(c, is[1], 64, &sg);
-  if (r0 == kBytesShape || r1 == kBytesShape || r2 == kBytesShape) return OURO_PACK_ESHAPE;
-  if (r0 | r1 | r2) return OURO_PACK_ESIZE;
-  if (er) byron_env(c, base, h, false, fs[1], cs[0], cs[2], epoch_slots, er);
-  if (!kRows) return OURO_PACK_OK;
-  const uint64_t m = magic_cfg < 0 ? magic : (uint64_t)magic_cfg;
-  uint8_t* d = o.msg + o.msg_off[i];
-  uint64_t n = 0;
-  d[n++] = '0';
-  d[n++] = '1';
-  n += put_span(d + n, c, (uint64_t)(gvk - c.b), (uint64_t)(gvk - c.b) + 64);
-  d[n++] = 0x09;
-  n += (uint64_t)put_uint(d + n, m);
-  d[n++] = 0x85;  // ToSign: encodeListLen 5
-  n += put_span(d + n, c, fs[1], fe[1]);  // prevHash
-  n += put_span(d + n, c, fs[2], fe[2]);  // bodyProof
-  n += put_span(d + n, c, cs[0], ce[0]);  // slotId
-  n += put_span(d + n, c, cs[2], ce[2]);  // difficulty
-  n += put_span(d + n, c, fs[4], fe[4]);  // extraData
-  o.msg_len[i] = (uint32_t)n;
-  const uint64_t g0 = (uint64_t)(gvk - c.b), d0 = (uint64_t)(dvk - c.b), s0 = (uint64_t)(sg - c.b);
-  put_span(o.pk + 32 * i, c, d0, d0 + 32);
-  put_span(o.sig + 64 * i, c, s0, s0 + 64);
-  put_span(o.genesis_vk + 64 * i, c, g0, g0 + 64);
-  put_span(o.delegate_vk + 64 * i, c, d0, d0 + 64);
-  o.magic[i] = magic;
-  return OURO_PACK_OK;
+  return byron_fields<kRows>(c, h, base, magic_cfg, o, i, er, epoch_slots, c.n);
 }
 
 OURO_HD inline void byron_zero_row(const ByronOut& o, size_t i) {

@@ -169,6 +169,75 @@ int launch_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
                           const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
                           uint8_t* verdict, uint32_t* n_bad);
 
+// the Byron whole-block integrity kernels (kernels_byron_block.hip;
+// cbor_byron_block.h), each checking its own launches.  Every pointer is device
+// memory.  The rows of one sequence over n blocks (byron_block_api.cpp lays
+// them out; each array 64-byte aligned):
+struct ByronBlockDev {
+  uint32_t *ntx, *gather_n, *msg_n;  // n each: the count pass
+  uint64_t *sums, *rows;             // 3 * byron_block_scan_tiles(n); 6: capped totals, totals
+  // n + 1 each ([n] = the totals); msg_off is the third.  msg_off is a scan only
+  // until the emit pass: emit leaves a block's own begin where it wrote a
+  // message and puts 0 where it wrote none (an EBB, a block that does not
+  // slice or does not fit), so that the signature launch reads inside the
+  // message area; [n] stays the total.  tx_begin and g_begin stay scans.
+  uint64_t *tx_begin, *g_begin;
+  // the Byron rows of the blocks (cbor_byron.h ByronOut; msg_off n + 1, msg: msg_cap bytes)
+  uint8_t *pk, *sig, *genesis_vk, *delegate_vk, *msg;
+  uint64_t *msg_off, *magic;
+  uint32_t* msg_len;
+  // per block: claimed hashes (n x 128), txpNumber, the dlg / upd spans (2n),
+  // the gathered witness list's span; per tx row: the tx span; the gather
+  // area (gather_cap bytes, allocated up to the next multiple of 4)
+  uint8_t* claimed;
+  uint32_t* tx_num;
+  uint64_t* seg_off;
+  uint32_t* seg_len;
+  uint64_t* g_off;
+  uint32_t* g_len;
+  uint64_t* tx_off;
+  uint32_t* tx_len;
+  uint8_t* gather;
+  // digests: leaves (tx_cap x 32), roots and witness lists (n x 32 each), dlg
+  // and upd (2n x 32); the signature verdicts (n); launch_blake2b's work (2n items)
+  uint8_t *leaf, *root, *wit_digest, *seg_digest, *sig_ok;
+  void* b2b;
+};
+// count: status, ntx, gathered witness bytes and message bytes per block
+// (zeros unless the status is OURO_PACK_OK); magic: the configured
+// ProtocolMagicId or -1 (it decides the message's length)
+int launch_byron_block_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes,
+                             const uint64_t* off, const uint32_t* len, size_t n, int64_t magic,
+                             uint8_t* status, uint32_t* ntx, uint32_t* gather, uint32_t* msg);
+// the exclusive scan of the three count arrays (n + 1 each, [n] = the totals);
+// rows[q] = min(total, capacity), rows[3 + q] = total
+size_t byron_block_scan_tiles(size_t n);
+int launch_byron_block_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* gather,
+                            const uint32_t* msg, uint64_t* sums, uint64_t* tx_begin,
+                            uint64_t* g_begin, uint64_t* msg_begin, size_t tx_cap,
+                            size_t gather_cap, size_t msg_cap, uint64_t* rows);
+// every tx row to "not written", then the emit pass of the blocks that fit
+// (OURO_PACK_ECAP for a regular one that does not; zero rows for every block
+// nothing is emitted for)
+int launch_byron_block_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off,
+                            const uint32_t* len, size_t n, int64_t magic, const uint32_t* ntx,
+                            const uint32_t* gather, const uint32_t* msg, const uint64_t* tx_begin,
+                            const uint64_t* g_begin, size_t tx_cap, size_t gather_cap,
+                            size_t msg_cap, const ByronBlockDev& d, uint8_t* status);
+// leaf digests of the tx rows (the row count read from rows[0]; raw 4-byte aligned)
+int launch_byron_leaf_hash(hipStream_t st, size_t tx_cap, const uint64_t* rows, const uint8_t* raw,
+                           size_t raw_bytes, const uint64_t* tx_off, const uint32_t* tx_len,
+                           uint8_t* digest);
+// root[i] = the Merkle root of block i's leaf digests (reduced in place)
+int launch_byron_merkle(hipStream_t st, size_t n, const uint8_t* status, const uint32_t* ntx,
+                        const uint64_t* tx_begin, uint8_t* digest, uint8_t* root);
+// verdict[i] = OURO_BYB_* bits; tx_root (optional): n x 32, 16-byte aligned
+int launch_byron_block_finish(hipStream_t st, size_t n, int64_t magic, const uint8_t* status,
+                              const uint32_t* ntx, const uint32_t* tx_num,
+                              const uint64_t* hdr_magic, const uint8_t* claimed,
+                              const uint8_t* root, const uint8_t* wit, const uint8_t* seg,
+                              const uint8_t* sig_ok, uint8_t* verdict, uint8_t* tx_root);
+
 // the forging-side kernels (kernels_forge.hip; forge.h), each checking its own
 // launch, on k_ed25519_verify's launch shape and scratch slots.  Every pointer
 // is device memory, 16-byte aligned.

@@ -191,33 +191,7 @@ size_t group_budget() {
   const size_t b = ouro_knobs::get().witness_group_bytes.load(std::memory_order_relaxed);
   return b ? b : kGroupBytes;
 }
-// the end of the group of whole blocks that starts at lo: as many as the byte
-// budget holds, at least one
-size_t group_end(const uint32_t* len, size_t n, size_t lo, size_t budget) {
-  size_t hi = lo, bytes = 0;
-  while (hi < n && (hi == lo || bytes + len[hi] <= budget)) bytes += len[hi++];
-  return hi;
-}
-// a group's raw bytes and spans on the device; the raw buffer is allocated up
-// to the next multiple of 4 (the kernels read the aligned dwords a span touches)
-struct GroupUp {
-  Window w;
-  const uint8_t* raw = nullptr;
-  const uint64_t* off = nullptr;
-  const uint32_t* len = nullptr;
-};
-int group_upload(Stager& sg, hipStream_t st, const uint8_t* raw, const uint64_t* off,
-                 const uint32_t* len, size_t m, GroupUp* g) {
-  if (int rc = window_of(m, off, len, &g->w)) return rc;
-  uint8_t* d = sg.out<uint8_t>(g->w.span() + 4);
-  g->off = sg.up(g->w.off.data(), m);
-  g->len = sg.up(len, m);
-  if (sg.rc) return sg.rc;
-  if (g->w.span())
-    OURO_HIP(hipMemcpyAsync(d, raw + g->w.lo, g->w.span(), hipMemcpyHostToDevice, st));
-  g->raw = d;
-  return OURO_OK;
-}
+// (the groups of whole blocks and their upload: host_util.h group_end, group_upload)
 
 int count_dev(const uint8_t* raw, const uint64_t* off, const uint32_t* len, size_t n,
               uint8_t* status, uint32_t* ntx, uint32_t* nwit) {
