@@ -605,8 +605,9 @@ int ouro_block_integrity_verify_cbor_device(void *stream, const uint8_t *raw, si
  *     `stream`, not synchronised, no host round trip between slicing and
  *     verifying; a span outside raw_bytes is per-block status OURO_PACK_ESPAN;
  *     rows past the blocks that fit are zero.
- * Out of scope: the bootstrap address check and every other UTXOW rule, Byron
- * witnesses, _multi forms, the chunked raw pipeline. */
+ * Out of scope: the bootstrap address check and every other UTXOW rule, _multi
+ * forms, the chunked raw pipeline.  Byron blocks' witnesses:
+ * ouro_byron_block_witness_verify_cbor below. */
 #define OURO_WIT_ALL_OK 0x01u
 typedef struct {
   size_t tx_cap, wit_cap;
@@ -729,7 +730,8 @@ int ouro_byron_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t 
  * tree shape for n >= 2 and the empty root; non-canonical or indefinite
  * encodings inside a witness vector (the reference may re-serialise there;
  * this library hashes the bytes as they stand); that the SSC proof's content
- * is ignored.  Byron transaction witnesses are not verified.
+ * is ignored.  The transaction witnesses are not verified here:
+ * ouro_byron_block_witness_verify_cbor below.
  * Outputs: status[i] = OURO_PACK_* (OK, ECBOR, ESHAPE, ESIZE, EBB, ESHELLEY;
  * ESPAN and ECAP from the _device form); verdict[i] = OURO_BYB_* bits, 0 for a
  * block that does not slice; tx_root (n x 32, may be NULL) the computed Merkle
@@ -755,8 +757,7 @@ int ouro_byron_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t 
  *     pass a capacity writes nothing and has status OURO_PACK_ECAP, verdict 0;
  *     the blocks that fit are a prefix of the regular ones.
  * Out of scope: one entry for mixed eras (partition a stream by the block tag),
- * _multi forms, the chunked raw pipeline, Byron transaction witnesses, the
- * latency plans. */
+ * _multi forms, the chunked raw pipeline, the latency plans. */
 #define OURO_BYB_HDR_OK 0x01u    /* verifyHeaderIntegrity                 */
 #define OURO_BYB_BODY_OK 0x02u   /* blockMatchesHeader: all five below    */
 #define OURO_BYB_TXNUM_OK 0x04u
@@ -790,6 +791,106 @@ int ouro_byron_block_integrity_verify_cbor_device(void *stream, const uint8_t *r
                                                   size_t gather_cap, size_t msg_cap, void *work,
                                                   size_t work_bytes, uint8_t *status,
                                                   uint8_t *verdict, uint8_t *tx_root);
+
+/* Byron transaction witnesses straight from raw block CBOR: the ByronDSIGN
+ * verification of every witness of every transaction over its signed message,
+ * the crypto call of CC.validateBlock with BlockValidation (ouroboros-consensus-
+ * byron/src/Ouroboros/Consensus/Byron/Ledger/Ledger.hs:190,346): one signature
+ * per transaction input.  The entries follow ouro_block_witness_* above (rows,
+ * capacities and the prefix property, OURO_PACK_ECAP, the row arrays) and
+ * ouro_byron_block_integrity_verify_cbor in the block forms and statuses: block
+ * i is raw[off[i] .. off[i] + len[i]) in either Byron form; everything outside
+ * the witness vectors keeps that entry's acceptance, status for status.  Tag 0
+ * (an EBB) is status OURO_PACK_EBB with verdict OURO_BYW_ALL_OK and no rows, a
+ * tag >= 2 OURO_PACK_ESHELLEY.  Every txPayload element is [tx, witnesses]:
+ *   witnesses = [* [type: uint, #6.24(bytes .cbor [key: bytes, sig: bytes])]]
+ *     definite or indefinite; each element a definite array(2); the tag-24
+ *     payload a definite byte string whose content is a definite array(2) of
+ *     two definite byte strings and ends exactly at the payload's end
+ *   type 0 (VKWitness):     key bytes(64) (an XPub), sig bytes(64)
+ *   type 2 (RedeemWitness): key bytes(32),           sig bytes(64)
+ * Any other type, major type, tag or array length is OURO_PACK_ESHAPE for the
+ * block; content malformed inside the payload or not ending at its end
+ * OURO_PACK_ECBOR; a wrong string length OURO_PACK_ESIZE -- per witness the
+ * content is walked first, then the two types, then the two sizes.  The status
+ * is that of the first offending item in byte order; malformed CBOR anywhere
+ * inside a [tx, witnesses] element is found by the outer walk before the
+ * element's witness vector is read.  A block that does not slice owns no rows.
+ * tx id = Blake2b-256 of the tx item's bytes as they stand (no prefix byte: not
+ * the Merkle leaf).  The signed message is
+ *   tag || CBOR(magic) || 0x58 0x20 || tx_id
+ * with tag 0x01 (SignTx) for type 0 and 0x02 (SignRedeemTx) for type 2, and
+ * magic the configured protocol_magic, or for -1 each block header's own field
+ * (mainnet, type 0: 01 1a 2d 96 4a 09 58 20).  Both kinds verify under
+ * ByronDSIGN acceptance (ouro_byron_ed25519_verify_batch's): type 0 under
+ * XPub[0:32], type 2 under the 32-byte redeem key.
+ * Pinned by the reference's golden Byron block: the witness vector's shape
+ * (81 82 00 d8 18 58 85 82 58 40 <64> 58 40 <64>).  NOT pinned by any reference
+ * fixture (restated from cardano-ledger's Cardano.Chain.UTxO.TxWitness and
+ * Cardano.Crypto.Signing.Tag, outside the reference tree, which only names
+ * SignTx at Byron/Crypto/DSIGN.hs:59): the signed message (the tag bytes and
+ * the 58 20 wrapped id); that the tx id hashes the bytes as they stand; that
+ * the redeem kind uses ByronDSIGN's acceptance rules; that an unknown witness
+ * type fails the block's decode.  The golden GenTxId_Byron is the example's
+ * input id, not this transaction's, and pins nothing here.
+ * Outputs: status[i] = OURO_PACK_*; n_bad[i] = the block's rows that do not
+ * verify; verdict[i] = OURO_BYW_ALL_OK iff the block sliced, fit and n_bad[i]
+ * == 0 (so also for a regular block without transactions) or is an EBB.
+ *   ouro_byron_block_witness_count_cbor[_host]: the count pass alone: status,
+ *     ntx[i] and nwit[i], zeros unless the status is OURO_PACK_OK.
+ *   ouro_byron_block_witness_verify_cbor: host buffers, synchronous, on the
+ *     calling thread's stream, in consecutive groups of whole blocks under a
+ *     byte budget (OURO_BYRON_WITNESS_GROUP_BYTES), each sized from its own
+ *     count pass; a device error recomputes the call on the host path.  Rows
+ *     past the blocks that fit are left untouched.
+ *   ouro_byron_block_witness_verify_cbor_host: the host path alone.
+ *   All four return OURO_EINVAL, before any work, for NULLs, a span outside
+ *   raw_bytes, or a protocol_magic outside -1 .. 2^32 - 1.
+ *   ouro_byron_block_witness_verify_cbor_device: device pointers (alignment
+ *     and work as for ouro_block_witness_verify_cbor_device, the work of
+ *     ouro_byron_block_witness_work_bytes(n, tx_cap, wit_cap) bytes), enqueued
+ *     on `stream`, not synchronised, no host round trip; a span outside
+ *     raw_bytes is per-block status OURO_PACK_ESPAN; rows past the blocks that
+ *     fit are zero.
+ * Out of scope: that a witness's key hashes to the spent output's address, that
+ * there is one witness per input, and every other UTxO rule (these need ledger
+ * state); delegation certificates and update proposals or votes inside the
+ * body (ouro_byron_dlg_cert_verify_batch serves a caller that has decoded
+ * them); the mempool's standalone GenTx form [0, [tx, witnesses]]; _multi
+ * forms; the chunked raw pipeline; fusing with the integrity entry; the latency
+ * plans. */
+#define OURO_BYW_ALL_OK 0x01u
+typedef struct {
+  size_t tx_cap, wit_cap;
+  uint64_t *tx_begin, *wit_begin; /* n + 1 each; [n] = totals, also when they pass the caps */
+  uint8_t *tx_id;                 /* tx_cap x 32 */
+  uint32_t *wit_tx;               /* wit_cap: global tx row */
+  uint8_t *wit_kind, *wit_ok;     /* wit_cap each: kind 0 = VKWitness, 2 = RedeemWitness; 1 = verifies */
+  uint8_t *wit_vk;                /* wit_cap x 64, may be NULL: the XPub; a redeem key then 32 zero bytes */
+} ouro_byron_block_witness_out;
+int ouro_byron_block_witness_count_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                        const uint32_t *len, size_t n, int64_t protocol_magic,
+                                        uint8_t *status, uint32_t *ntx, uint32_t *nwit);
+int ouro_byron_block_witness_count_cbor_host(const uint8_t *raw, size_t raw_bytes,
+                                             const uint64_t *off, const uint32_t *len, size_t n,
+                                             int64_t protocol_magic, uint8_t *status,
+                                             uint32_t *ntx, uint32_t *nwit);
+int ouro_byron_block_witness_verify_cbor(const uint8_t *raw, size_t raw_bytes, const uint64_t *off,
+                                         const uint32_t *len, size_t n, int64_t protocol_magic,
+                                         const ouro_byron_block_witness_out *out, uint8_t *status,
+                                         uint8_t *verdict, uint32_t *n_bad);
+int ouro_byron_block_witness_verify_cbor_host(const uint8_t *raw, size_t raw_bytes,
+                                              const uint64_t *off, const uint32_t *len, size_t n,
+                                              int64_t protocol_magic,
+                                              const ouro_byron_block_witness_out *out,
+                                              uint8_t *status, uint8_t *verdict, uint32_t *n_bad);
+size_t ouro_byron_block_witness_work_bytes(size_t n, size_t tx_cap, size_t wit_cap);
+int ouro_byron_block_witness_verify_cbor_device(void *stream, const uint8_t *raw, size_t raw_bytes,
+                                                const uint64_t *off, const uint32_t *len, size_t n,
+                                                int64_t protocol_magic,
+                                                const ouro_byron_block_witness_out *out, void *work,
+                                                size_t work_bytes, uint8_t *status,
+                                                uint8_t *verdict, uint32_t *n_bad);
 /* A raw header stream across eras and epochs in ONE call: what ChainDB's
  * re-validation of a stored suffix (LgrDB.hs:350-368), ImmutableDB /
  * VolatileDB replay and ChainSync windows of a Cardano chain actually hold --

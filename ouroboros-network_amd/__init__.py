@@ -10,6 +10,8 @@ from . import _native
 from ._native import DeviceError, NativeUnavailable
 from .block import blake2b256_batch, parse_block, verify_block_integrity_cbor
 from .byron_block import count_byron_blocks, parse_byron_block, verify_byron_block_integrity
+from .byron_witness import (byron_witness_message, count_byron_block_witnesses,
+                            parse_byron_witnesses, verify_byron_block_witnesses)
 from .byron import (ByronDSIGN, dlg_cert_message, pack_byron_cbor, parse_byron_header,
                     verify_byron_cbor, verify_byron_headers, verify_delegation_certs)
 from .dsign import Ed25519DSIGN
@@ -43,8 +45,10 @@ __all__ = [
     "Sum6KES",
     "blake2b256_batch",
     "byron_key_hash",
+    "byron_witness_message",
     "chain_envelope_cbor",
     "count_block_witnesses",
+    "count_byron_block_witnesses",
     "count_byron_blocks",
     "counter_fold",
     "first_invalid",
@@ -57,6 +61,7 @@ __all__ = [
     "parse_block",
     "parse_byron_block",
     "parse_byron_header",
+    "parse_byron_witnesses",
     "parse_witnesses",
     "pbft_checks",
     "pbft_rule",
@@ -67,6 +72,7 @@ __all__ = [
     "verify_block_integrity_cbor",
     "verify_block_witnesses",
     "verify_byron_block_integrity",
+    "verify_byron_block_witnesses",
     "verify_byron_cbor",
     "verify_byron_headers",
     "verify_chain_cbor",

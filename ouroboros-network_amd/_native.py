@@ -412,6 +412,17 @@ SIGNATURES = {
     "ouro_byron_block_integrity_verify_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ,
                                                            ctypes.c_int64, _SZ, _SZ, _SZ, _P, _SZ,
                                                            _P, _P, _P]),
+    "ouro_byron_block_witness_count_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_int64, _P, _P,
+                                                 _P]),
+    "ouro_byron_block_witness_count_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_int64, _P,
+                                                      _P, _P]),
+    "ouro_byron_block_witness_verify_cbor": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_int64, _P, _P,
+                                                  _P, _P]),
+    "ouro_byron_block_witness_verify_cbor_host": (_I, [_P, _SZ, _P, _P, _SZ, ctypes.c_int64, _P,
+                                                       _P, _P, _P]),
+    "ouro_byron_block_witness_work_bytes": (_SZ, [_SZ, _SZ, _SZ]),
+    "ouro_byron_block_witness_verify_cbor_device": (_I, [_P, _P, _SZ, _P, _P, _SZ, ctypes.c_int64,
+                                                         _P, _P, _SZ, _P, _P, _P]),
     "ouro_sum6kes_verify_batch": (_I, [_SZ, _P, _P, _P, _P, _P, _P, _P]),
     "ouro_tpraos_verify_batch": (_I, [ctypes.POINTER(TPraosBatch), _P, _P, _P]),
     "ouro_ed25519_verify_batch_device": (_I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),

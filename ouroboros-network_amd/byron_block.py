@@ -38,7 +38,8 @@ form and the two payload hashes.  NOT pinned by a reference fixture: the tree
 shape for n >= 2 and the empty root (restated from cardano-ledger's
 Cardano.Chain.Common.Merkle), non-canonical or indefinite encodings inside a
 witness vector (hashed here as they stand), that the SSC proof's content is
-ignored.  Byron transaction witnesses are not verified.
+ignored.  The transaction witnesses are not verified here: byron_witness.py
+ verifies them.
 """
 from __future__ import annotations
 
@@ -147,9 +148,11 @@ def _sized(buf, end, starts, want, what):
     return got
 
 
-def parse_byron_block(raw: bytes) -> Optional[ByronBlock]:
+def parse_byron_block(raw: bytes, visit=None) -> Optional[ByronBlock]:
     """Slice one block: a ByronBlock, or None for an EBB; raises
-    BlockError(status) where the C walker rejects."""
+    BlockError(status) where the C walker rejects.  visit(k, tx, wit): called
+    for the k-th [tx, witnesses] element once the walk has accepted it, with the
+    two (offset, length) spans -- the walker's visitor (byron_witness.py)."""
     buf = bytes(raw)
     end = len(buf)
     mt, arg, j = _head(buf, 0, end)
@@ -217,6 +220,8 @@ def parse_byron_block(raw: bytes) -> Optional[ByronBlock]:
             e = _skip(buf, a, end)
             spans.append((a, e - a))
             a = e
+        if visit is not None:
+            visit(len(txs), spans[0], spans[1])
         txs.append(spans[0])
         wits.append(spans[1])
         return a

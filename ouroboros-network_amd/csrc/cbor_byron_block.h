@@ -40,7 +40,8 @@
 // block decoder): the tree shape for n >= 2 and the empty root; non-canonical
 // or indefinite encodings inside a witness vector (the reference may
 // re-serialise there, this slicer hashes the bytes as they stand); that the
-// SSC proof's content is ignored.  Byron transaction witnesses are out of scope.
+// SSC proof's content is ignored.  The transaction witnesses are verified by
+// cbor_byron_witness.h's visitors over this walk, not here.
 #pragma once
 #include "blake2b_stream.h"
 #include "cbor_byron.h"

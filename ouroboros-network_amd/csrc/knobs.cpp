@@ -54,6 +54,8 @@ void load(Knobs& k) {
   read_size<size_t>(k.witness_group_bytes, "OURO_WITNESS_GROUP_BYTES", 0);
   // the same budget for ouro_byron_block_integrity_verify_cbor (byron_block_api.cpp)
   read_size<size_t>(k.byron_block_group_bytes, "OURO_BYRON_BLOCK_GROUP_BYTES", 0);
+  // ... and for ouro_byron_block_witness_verify_cbor (byron_witness_api.cpp)
+  read_size<size_t>(k.byron_witness_group_bytes, "OURO_BYRON_WITNESS_GROUP_BYTES", 0);
   read_int(k.lat_block, "OURO_LAT_BLOCK", 0);
   read_int(k.lat_quad, "OURO_LAT_QUAD", 1);
   read_int(k.lat_wide, "OURO_LAT_WIDE", 0xff);

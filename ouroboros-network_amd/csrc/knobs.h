@@ -38,6 +38,7 @@ struct Knobs {
   std::atomic<int> block_sort{1};            // OURO_BLOCK_SORT (0: hash work items unordered, A/B)
   std::atomic<size_t> witness_group_bytes{0};  // OURO_WITNESS_GROUP_BYTES (0: the default, 256 MiB)
   std::atomic<size_t> byron_block_group_bytes{0};  // OURO_BYRON_BLOCK_GROUP_BYTES (0: the default, 256 MiB)
+  std::atomic<size_t> byron_witness_group_bytes{0};  // OURO_BYRON_WITNESS_GROUP_BYTES (0: the default, 256 MiB)
   // latency mode (A/B forms, bit-exact; read when a plan / launch shape is made)
   std::atomic<int> lat_block{0};             // OURO_LAT_BLOCK (0: kLatBlock)
   std::atomic<int> lat_quad{1};              // OURO_LAT_QUAD

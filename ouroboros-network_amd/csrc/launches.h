@@ -238,6 +238,40 @@ int launch_byron_block_finish(hipStream_t st, size_t n, int64_t magic, const uin
                               const uint8_t* root, const uint8_t* wit, const uint8_t* seg,
                               const uint8_t* sig_ok, uint8_t* verdict, uint8_t* tx_root);
 
+// the Byron transaction-witness kernels (kernels_byron_witness.hip;
+// cbor_byron_witness.h), each checking its own launches.  Every pointer is
+// device memory.  They follow the launch_witness_* ones above; what differs:
+// count: status, ntx and nwit per block (zeros unless the status is OURO_PACK_OK)
+int launch_byron_witness_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes,
+                               const uint64_t* off, const uint32_t* len, size_t n, uint8_t* status,
+                               uint32_t* ntx, uint32_t* nwit);
+// sums: 2 * byron_witness_scan_tiles(n) words of work; rows[0..1] =
+// min(total, capacity), rows[2..3] = the totals
+size_t byron_witness_scan_tiles(size_t n);
+int launch_byron_witness_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* nwit,
+                              uint64_t* sums, uint64_t* tx_begin, uint64_t* wit_begin,
+                              size_t tx_cap, size_t wit_cap, uint64_t* rows);
+// vk and sig: wit_cap x 64 each (a redeem key then 32 zero bytes); magic: n,
+// the magic block i's messages use (magic_cfg, or -1: its header's own field)
+int launch_byron_witness_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off,
+                              const uint32_t* len, size_t n, int64_t magic_cfg, const uint32_t* ntx,
+                              const uint32_t* nwit, const uint64_t* tx_begin,
+                              const uint64_t* wit_begin, size_t tx_cap, size_t wit_cap,
+                              uint64_t tx_base, uint64_t* tx_off, uint32_t* tx_len, uint8_t* vk,
+                              uint8_t* sig, uint32_t* wit_tx, uint8_t* kind, uint64_t* magic,
+                              uint8_t* status);
+// ByronDSIGN per witness row under vk[0:32] over tag || CBOR(magic) || 58 20 ||
+// tx id, the message built in the lane (wit_begin, n, magic: the row's block)
+int launch_byron_witness_verify(hipStream_t st, size_t wit_cap, const uint64_t* rows,
+                                const uint8_t* vk, const uint8_t* sig, const uint32_t* wit_tx,
+                                const uint8_t* tx_id, size_t tx_cap, uint64_t tx_base,
+                                const uint64_t* wit_begin, size_t n, const uint64_t* magic,
+                                uint8_t* kind, uint8_t* wit_ok);
+// verdict[i] = OURO_BYW_ALL_OK for an EBB too
+int launch_byron_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
+                                const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
+                                uint8_t* verdict, uint32_t* n_bad);
+
 // the forging-side kernels (kernels_forge.hip; forge.h), each checking its own
 // launch, on k_ed25519_verify's launch shape and scratch slots.  Every pointer
 // is device memory, 16-byte aligned.
