@@ -28,7 +28,6 @@ using namespace ouro_rt;
 
 namespace {
 
-constexpr size_t kGroupBytes = (size_t)256 << 20;  // OURO_BYRON_BLOCK_GROUP_BYTES' default
 using Dev = ByronBlockDev;
 
 // ---- the rows of one sequence as one area, each array 64-byte aligned ----
@@ -44,7 +43,7 @@ size_t carve_counts(uint8_t* a, size_t n, Dev* d) {
   put(&d->ntx, a, &at, 4 * n);
   put(&d->gather_n, a, &at, 4 * n);
   put(&d->msg_n, a, &at, 4 * n);
-  put(&d->sums, a, &at, 24 * byron_block_scan_tiles(n));
+  put(&d->sums, a, &at, 24 * scan_tiles(n));
   put(&d->rows, a, &at, 64);
   put(&d->tx_begin, a, &at, 8 * (n + 1));
   put(&d->g_begin, a, &at, 8 * (n + 1));
@@ -219,17 +218,14 @@ void totals_of(size_t n, const uint32_t* ntx, const uint32_t* gather, const uint
 }
 
 // ---- the host-buffer forms on the device ----
-size_t group_budget() {
-  const size_t b = ouro_knobs::get().byron_block_group_bytes.load(std::memory_order_relaxed);
-  return b ? b : kGroupBytes;
-}
+size_t budget_bytes() { return group_budget(ouro_knobs::get().byron_block_group_bytes); }
 
 int count_dev(const uint8_t* raw, const uint64_t* off, const uint32_t* len, size_t n, int64_t magic,
               uint8_t* status, uint32_t* ntx, uint32_t* gather, uint32_t* msg) {
   hipStream_t st;
   int rc = thread_stream(&st);
   if (rc) return rc;
-  const size_t budget = group_budget();
+  const size_t budget = budget_bytes();
   for (size_t lo = 0; lo < n;) {
     const size_t hi = group_end(len, n, lo, budget), m = hi - lo;
     Stager sg{st};
@@ -264,7 +260,7 @@ int byb_dev(const uint8_t* raw, const uint64_t* off, const uint32_t* len, size_t
   hipStream_t st;
   int rc = thread_stream(&st);
   if (rc) return rc;
-  const size_t budget = group_budget();
+  const size_t budget = budget_bytes();
   for (size_t lo = 0; lo < n;) {
     const size_t hi = group_end(len, n, lo, budget), m = hi - lo;
     Stager sg{st};

@@ -5,6 +5,7 @@
 // (hidden visibility), like runtime.h.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <string>
 
 #include "../../include/ouro_verify.h"
@@ -69,7 +70,12 @@ inline bool misaligned(const void* p, size_t k) {
   return (reinterpret_cast<uintptr_t>(p) & (k - 1)) != 0;
 }
 
-// ---- host-buffer block batches in groups (witness_api.cpp, byron_block_api.cpp) ----
+// ---- host-buffer block batches in groups (witness_flow.h, byron_block_api.cpp) ----
+// a group's byte budget: the entry's *_group_bytes knob (knobs.h), or its default
+inline size_t group_budget(const std::atomic<size_t>& knob, size_t dflt = (size_t)256 << 20) {
+  const size_t b = knob.load(std::memory_order_relaxed);
+  return b ? b : dflt;
+}
 // the end of the group of whole blocks that starts at lo: as many as the byte
 // budget holds, at least one
 inline size_t group_end(const uint32_t* len, size_t n, size_t lo, size_t budget) {

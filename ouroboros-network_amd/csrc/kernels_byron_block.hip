@@ -7,7 +7,7 @@
 // built exactly as before.  The launches take plain pointers only.
 //
 // The sequence (byron_block_api.cpp byb_count_scan, byb_rows): count (one lane
-// per block), a two-level exclusive scan of the three count arrays, clear, emit
+// per block), the three-value exclusive scan (scan_excl.h), clear, emit
 // (one lane per block, at the rows the scan gave it: no atomics), the leaf
 // hashes (one lane per transaction row), the Merkle roots (one lane per
 // block), the plain hashes and the ByronDSIGN launch (kernels.hip's
@@ -24,6 +24,7 @@
 #include "launch.h"
 #include "launches.h"
 #include "runtime.h"
+#include "scan_excl.h"
 
 using namespace ouro;
 using namespace ouro_rt;
@@ -47,134 +48,6 @@ __global__ void __launch_bounds__(kBlock) k_byron_block_count(
     stg1(ntx + i, (int32_t)a);
     stg1(gather + i, (int32_t)b);
     stg1(msg + i, (int32_t)c);
-  }
-}
-
-// ---- the exclusive scan of the three count arrays, in two levels ----
-// kernels_witness.hip's scan with a third value (an instance of its own: that
-// unit's kernels stay exactly as they are).  A tile is kScanTile consecutive
-// blocks, kScanPer per thread of one workgroup.  Level 1 reduces every tile,
-// level 2 (ONE workgroup) scans the tile sums in place and writes the totals,
-// and the apply kernel scans inside each tile on top of its tile's prefix.
-constexpr int kScanPer = 4;
-constexpr int kScanTile = kBlock * kScanPer;
-constexpr int kScanVals = 3;  // ntx, gather bytes, message bytes
-
-// the exclusive prefix of one triple per thread over the workgroup's kBlock
-// threads, and the workgroup's totals (every thread calls it)
-__device__ __forceinline__ void wg_excl_scan3(uint64_t v[kScanVals], uint64_t tot[kScanVals]) {
-  __shared__ uint64_t s[kScanVals][kBlock];
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < kScanVals; q++) s[q][t] = v[q];
-  __syncthreads();
-  for (int d = 1; d < kBlock; d <<= 1) {  // Hillis-Steele, inclusive
-    uint64_t x[kScanVals];
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++) x[q] = t >= d ? s[q][t - d] : 0;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++) s[q][t] += x[q];
-    __syncthreads();
-  }
-  uint64_t e[kScanVals];
-#pragma unroll
-  for (int q = 0; q < kScanVals; q++) {
-    tot[q] = s[q][kBlock - 1];
-    e[q] = s[q][t] - v[q];
-  }
-  __syncthreads();  // (the arrays are reused by the caller's next tile)
-#pragma unroll
-  for (int q = 0; q < kScanVals; q++) v[q] = e[q];
-}
-
-struct ScanIn {
-  const uint32_t* c[kScanVals];
-};
-struct ScanOut {
-  uint64_t* b[kScanVals];  // n + 1 each
-};
-
-// sums[3 k + q] = the sum of count array q over tile k
-__global__ void __launch_bounds__(kBlock) k_byron_block_tile_sums(size_t n, ScanIn in,
-                                                                  uint64_t* __restrict__ sums) {
-  const size_t tiles = (n + kScanTile - 1) / kScanTile;
-  for (size_t k = blockIdx.x; k < tiles; k += gridDim.x) {  // (whole workgroups: the barriers)
-    uint64_t v[kScanVals] = {0, 0, 0}, tot[kScanVals];
-    for (int p = 0; p < kScanPer; p++) {
-      const size_t i = k * kScanTile + (size_t)threadIdx.x * kScanPer + p;
-      if (i < n)
-#pragma unroll
-        for (int q = 0; q < kScanVals; q++) v[q] += (uint32_t)ldg1(in.c[q] + i);
-    }
-    wg_excl_scan3(v, tot);
-    if (threadIdx.x == 0)
-#pragma unroll
-      for (int q = 0; q < kScanVals; q++) stg8(sums + kScanVals * k + q, tot[q]);
-  }
-}
-
-// one workgroup: the tile sums to their exclusive prefixes, in place (each
-// thread a run of consecutive tiles); the totals to begin[q][n], to rows[3 + q]
-// and, capped, rows[q] = min(total, capacity): what the later kernels read
-struct ScanCaps {
-  uint64_t cap[kScanVals];
-};
-__global__ void __launch_bounds__(kBlock) k_byron_block_scan_sums(size_t n,
-                                                                  uint64_t* __restrict__ sums,
-                                                                  ScanOut out, ScanCaps caps,
-                                                                  uint64_t* __restrict__ rows) {
-  const size_t tiles = (n + kScanTile - 1) / kScanTile;
-  const size_t per = (tiles + kBlock - 1) / kBlock;
-  const size_t lo = (size_t)threadIdx.x * per < tiles ? (size_t)threadIdx.x * per : tiles;
-  const size_t hi = lo + per < tiles ? lo + per : tiles;
-  uint64_t v[kScanVals] = {0, 0, 0}, tot[kScanVals];
-  for (size_t k = lo; k < hi; k++)
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++) v[q] += ldg8(sums + kScanVals * k + q);
-  wg_excl_scan3(v, tot);
-  for (size_t k = lo; k < hi; k++)
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++) {
-      const uint64_t x = ldg8(sums + kScanVals * k + q);
-      stg8(sums + kScanVals * k + q, v[q]);
-      v[q] += x;
-    }
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++) {
-      stg8(out.b[q] + n, tot[q]);
-      stg8(rows + q, tot[q] < caps.cap[q] ? tot[q] : caps.cap[q]);
-      stg8(rows + kScanVals + q, tot[q]);
-    }
-}
-
-// begin[q][i] for i < n: the tile's prefix + the scan inside it
-__global__ void __launch_bounds__(kBlock) k_byron_block_scan_apply(size_t n, ScanIn in,
-                                                                   const uint64_t* __restrict__ sums,
-                                                                   ScanOut out) {
-  const size_t tiles = (n + kScanTile - 1) / kScanTile;
-  for (size_t k = blockIdx.x; k < tiles; k += gridDim.x) {
-    const size_t i0 = k * kScanTile + (size_t)threadIdx.x * kScanPer;
-    uint32_t c[kScanVals][kScanPer];
-    uint64_t v[kScanVals] = {0, 0, 0}, tot[kScanVals];
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++)
-#pragma unroll
-      for (int p = 0; p < kScanPer; p++) {
-        c[q][p] = i0 + p < n ? (uint32_t)ldg1(in.c[q] + i0 + p) : 0u;
-        v[q] += c[q][p];
-      }
-    wg_excl_scan3(v, tot);
-#pragma unroll
-    for (int q = 0; q < kScanVals; q++) {
-      uint64_t a = v[q] + ldg8(sums + kScanVals * k + q);
-#pragma unroll
-      for (int p = 0; p < kScanPer; p++) {
-        if (i0 + p < n) stg8(out.b[q] + i0 + p, a);
-        a += c[q][p];
-      }
-    }
   }
 }
 
@@ -228,7 +101,7 @@ __global__ void __launch_bounds__(kBlock) k_byron_block_emit(
 // transaction row in row order (workgroups of one wave, as k_header_hash).  No
 // length-class sort: Byron transactions lie within a few compressions of each
 // other, and the rows of a block stay neighbours for k_byron_merkle.  The row
-// count comes from device memory (rows[0], k_byron_block_scan_sums).  raw must
+// count comes from device memory (rows[0], the scan).  raw must
 // be 4-byte aligned.  A row nothing was emitted to gets zeros.
 constexpr int kLeafBlock = 64;
 __global__ void __launch_bounds__(kLeafBlock) k_byron_leaf_hash(
@@ -304,8 +177,6 @@ static unsigned lane_grid(size_t n) {
 
 namespace ouro_rt {
 
-size_t byron_block_scan_tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; }
-
 int launch_byron_block_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes,
                              const uint64_t* off, const uint32_t* len, size_t n, int64_t magic,
                              uint8_t* status, uint32_t* ntx, uint32_t* gather, uint32_t* msg) {
@@ -320,13 +191,11 @@ int launch_byron_block_scan(hipStream_t st, size_t n, const uint32_t* ntx, const
                             uint64_t* g_begin, uint64_t* msg_begin, size_t tx_cap,
                             size_t gather_cap, size_t msg_cap, uint64_t* rows) {
   if (n == 0) return OURO_OK;
-  const unsigned tiles = (unsigned)std::min<size_t>(byron_block_scan_tiles(n), 4096);
-  const ScanIn in{{ntx, gather, msg}};
-  const ScanOut out{{tx_begin, g_begin, msg_begin}};
-  const ScanCaps caps{{(uint64_t)tx_cap, (uint64_t)gather_cap, (uint64_t)msg_cap}};
-  hipLaunchKernelGGL(k_byron_block_tile_sums, dim3(tiles), dim3(kBlock), 0, st, n, in, sums);
-  hipLaunchKernelGGL(k_byron_block_scan_sums, dim3(1), dim3(kBlock), 0, st, n, sums, out, caps, rows);
-  hipLaunchKernelGGL(k_byron_block_scan_apply, dim3(tiles), dim3(kBlock), 0, st, n, in, sums, out);
+  // (ntx, gather bytes, message bytes)
+  const scan::Args<3> a{{ntx, gather, msg},
+                        {tx_begin, g_begin, msg_begin},
+                        {(uint64_t)tx_cap, (uint64_t)gather_cap, (uint64_t)msg_cap}};
+  scan::launch<3>(st, n, a, sums, rows);
   return launch_check();
 }
 

@@ -6,71 +6,40 @@
 // verify.h's lane routines, and its copies (and those of the slicers) live in
 // namespace ouro_byw, so no symbol is shared with the other units' and every
 // kernel there is built exactly as before.  The launches take plain pointers
-// only (no type of the renamed namespace crosses to the host units).
+// only, one struct of them (launches.h WitnessDev): no type of the renamed
+// namespace crosses to the host units.
 //
-// The sequence (byron_witness_api.cpp byw_count_scan, byw_rows): count (one
-// lane per block), the two-value exclusive scan (scan_excl.h), clear, emit (one
-// lane per block, at the rows the scan gave it: no atomics), the tx ids
-// (kernels.hip's launch_blake2b over the emitted spans), verify (one lane per
-// witness row, the row count read from device memory, the signed message built
-// in the lane), the tail and finish (one lane per block).
+// The sequence (witness_flow.h count_scan, rows): count (one lane per block),
+// the two-value exclusive scan (scan_excl.h), clear, emit (one lane per block,
+// at the rows the scan gave it: no atomics), the tx ids (kernels.hip's
+// launch_blake2b over the emitted spans), verify (one lane per witness row, the
+// row count read from device memory, the signed message built in the lane),
+// the tail and finish (one lane per block).  Count, clear, tail and finish are
+// witness_kernels.h's, shared with kernels_witness.hip; emit and verify are
+// this era's own.
 #define ouro ouro_byw
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
 
 #include "../../include/ouro_verify.h"
 #include "cbor_byron_witness.h"
 #include "launch.h"
 #include "launches.h"
 #include "runtime.h"
-#include "scan_excl.h"
+#include "witness_kernels.h"
 
 using namespace ouro;
 using namespace ouro_rt;
 
-// one lane per block: the count pass; zeros unless the block is a regular
-// block that slices
-__global__ void __launch_bounds__(kBlock) k_byron_witness_count(
-    const uint8_t* __restrict__ raw, size_t raw_bytes, const uint64_t* __restrict__ off,
-    const uint32_t* __restrict__ len, size_t n, uint8_t* __restrict__ status,
-    uint32_t* __restrict__ ntx, uint32_t* __restrict__ nwit) {
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nth = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid; i < n; i += nth) {
-    const uint64_t o0 = ldg8(off + i);
-    const uint32_t l0 = (uint32_t)ldg1(len + i);
-    uint32_t a = 0, b = 0;
-    const uint8_t st = (o0 > raw_bytes || raw_bytes - o0 < l0)
-                           ? (uint8_t)OURO_PACK_ESPAN
-                           : cbor::byron_witness_count_one(raw, o0, l0, &a, &b);
-    status[i] = st;
-    stg1(ntx + i, (int32_t)a);
-    stg1(nwit + i, (int32_t)b);
+// the era trait of witness_kernels.h
+struct ByronWit {
+  static constexpr int kKeyBytes = 64;
+  static constexpr uint8_t kAllOk = OURO_BYW_ALL_OK;
+  static constexpr bool kEbbOk = true;
+  static __device__ __forceinline__ uint8_t count_one(const uint8_t* raw, uint64_t base,
+                                                      uint32_t len, uint32_t* ntx, uint32_t* nwit) {
+    return cbor::byron_witness_count_one(raw, base, len, ntx, nwit);
   }
-}
-
-// Every row up to the capacities to "not written": a tx span outside the raw
-// buffer (k_blake2b256 then writes a zero digest), a witness row of kind
-// kBywUnwritten (k_byron_witness_verify then writes zeros) with a zero key, so
-// that the rows of a block that did not fit, and those past the totals, read
-// as zero.
-constexpr uint8_t kBywUnwritten = 0xff;
-__global__ void __launch_bounds__(kBlock) k_byron_witness_clear(
-    size_t tx_cap, size_t wit_cap, uint64_t* __restrict__ tx_off, uint32_t* __restrict__ tx_len,
-    uint32_t* __restrict__ wit_tx, uint8_t* __restrict__ kind, uint8_t* __restrict__ vk) {
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nth = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid; i < tx_cap; i += nth) {
-    stg8(tx_off + i, ~0ull);
-    stg1(tx_len + i, 0);
-  }
-  for (size_t i = tid; i < wit_cap; i += nth) {
-    stg1(wit_tx + i, 0);
-    kind[i] = kBywUnwritten;
-    cbor::zero_bytes(vk + 64 * i, 64);
-  }
-}
+};
 
 // one lane per block: the emit pass of a sliced block whose rows fit, at the
 // rows the scan gave it, and the magic its messages use (the configured one,
@@ -142,7 +111,7 @@ struct ShaByronTxTail {
 // the scan).  The message is built in the lane from the row's kind, its
 // block's magic (blk: the row's block, found from wit_begin by bisection) and
 // its transaction id (tx_id row wit_tx - tx_base).  A row nothing was emitted
-// to (kBywUnwritten) gets zeros.
+// to (wit::kUnwritten) gets zeros.
 __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_byron_witness_verify(
     const uint64_t* __restrict__ rows, const uint8_t* __restrict__ vk,
     const uint8_t* __restrict__ sig, const uint32_t* __restrict__ wit_tx,
@@ -158,7 +127,7 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_byron_witness_verify(
     // wit_tx is the global row; tx_id holds this call's rows, the first tx_base
     const uint64_t t = (uint64_t)(uint32_t)ldg1(wit_tx + i) - tx_base;
     const uint8_t kd = kind[i];
-    if (kd == kBywUnwritten || t >= tx_cap) {  // (t < tx_cap always for an emitted row)
+    if (kd == wit::kUnwritten || t >= tx_cap) {  // (t < tx_cap always for an emitted row)
       kind[i] = 0;
       wit_ok[i] = 0;
       continue;
@@ -184,112 +153,49 @@ __global__ void __launch_bounds__(kBlock, OURO_WAVES) k_byron_witness_verify(
     wit_ok[i] = ok ? 1 : 0;
   }
 }
-// the rows from the row count to the capacity: zeros (a kernel of its own, so
-// that the verify kernel's loop is k_ed25519_verify's)
-__global__ void __launch_bounds__(kBlock) k_byron_witness_tail(const uint64_t* __restrict__ rows,
-                                                               size_t wit_cap,
-                                                               uint8_t* __restrict__ kind,
-                                                               uint8_t* __restrict__ wit_ok) {
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nth = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)ldg8(rows + 1) + tid; i < wit_cap; i += nth) {
-    kind[i] = 0;
-    wit_ok[i] = 0;
-  }
-}
-
-// one lane per block: n_bad[i] = its witness rows with wit_ok == 0; verdict[i]
-// = OURO_BYW_ALL_OK iff the block sliced, fit and n_bad == 0, or is an EBB
-__global__ void __launch_bounds__(kBlock) k_byron_witness_finish(
-    size_t n, const uint8_t* __restrict__ status, const uint64_t* __restrict__ wit_begin,
-    const uint8_t* __restrict__ wit_ok, uint64_t wit_cap, uint8_t* __restrict__ verdict,
-    uint32_t* __restrict__ n_bad) {
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t nth = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = tid; i < n; i += nth) {
-    uint32_t bad = 0;
-    uint8_t v = status[i] == OURO_PACK_EBB ? (uint8_t)OURO_BYW_ALL_OK : (uint8_t)0;
-    if (status[i] == OURO_PACK_OK) {
-      const uint64_t lo = ldg8(wit_begin + i), e = ldg8(wit_begin + i + 1);
-      const uint64_t hi = e < wit_cap ? e : wit_cap;
-      for (uint64_t r = lo; r < hi; r++) bad += ldg_u8(wit_ok + r) ? 0u : 1u;
-      v = bad == 0 ? (uint8_t)OURO_BYW_ALL_OK : (uint8_t)0;
-    }
-    stg1(n_bad + i, (int32_t)bad);
-    verdict[i] = v;
-  }
-}
-
-static unsigned lane_grid(size_t n) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>((n + kBlock - 1) / kBlock, 4096));
-}
 
 namespace ouro_rt {
-
-size_t byron_witness_scan_tiles(size_t n) { return scan::tiles(n); }
 
 int launch_byron_witness_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes,
                                const uint64_t* off, const uint32_t* len, size_t n, uint8_t* status,
                                uint32_t* ntx, uint32_t* nwit) {
-  if (n == 0) return OURO_OK;
-  hipLaunchKernelGGL(k_byron_witness_count, dim3(lane_grid(n)), dim3(kBlock), 0, st, raw, raw_bytes,
-                     off, len, n, status, ntx, nwit);
-  return launch_check();
+  return wit::launch_count<ByronWit>(st, raw, raw_bytes, off, len, n, status, ntx, nwit);
 }
 
-int launch_byron_witness_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* nwit,
-                              uint64_t* sums, uint64_t* tx_begin, uint64_t* wit_begin,
-                              size_t tx_cap, size_t wit_cap, uint64_t* rows) {
-  if (n == 0) return OURO_OK;
-  const scan::Args<2> a{{ntx, nwit}, {tx_begin, wit_begin}, {(uint64_t)tx_cap, (uint64_t)wit_cap}};
-  scan::launch<2>(st, n, a, sums, rows);
-  return launch_check();
+int launch_byron_witness_scan(hipStream_t st, size_t n, const WitnessDev& d) {
+  return wit::launch_scan(st, n, d);
 }
 
 int launch_byron_witness_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off,
-                              const uint32_t* len, size_t n, int64_t magic_cfg, const uint32_t* ntx,
-                              const uint32_t* nwit, const uint64_t* tx_begin,
-                              const uint64_t* wit_begin, size_t tx_cap, size_t wit_cap,
-                              uint64_t tx_base, uint64_t* tx_off, uint32_t* tx_len, uint8_t* vk,
-                              uint8_t* sig, uint32_t* wit_tx, uint8_t* kind, uint64_t* magic,
+                              const uint32_t* len, size_t n, int64_t magic_cfg, const WitnessDev& d,
                               uint8_t* status) {
   if (n == 0) return OURO_OK;
-  hipLaunchKernelGGL(k_byron_witness_clear, dim3(lane_grid(std::max(tx_cap, wit_cap))),
-                     dim3(kBlock), 0, st, tx_cap, wit_cap, tx_off, tx_len, wit_tx, kind, vk);
-  const cbor::BywRows rows{tx_off, tx_len, vk, sig, wit_tx, kind, tx_base};
-  hipLaunchKernelGGL(k_byron_witness_emit, dim3(lane_grid(n)), dim3(kBlock), 0, st, raw, off, len,
-                     n, magic_cfg, ntx, nwit, tx_begin, wit_begin, (uint64_t)tx_cap,
-                     (uint64_t)wit_cap, rows, magic, status);
+  wit::launch_clear<ByronWit>(st, d);
+  const cbor::BywRows rows{d.tx_off, d.tx_len, d.vk, d.sig, d.wit_tx, d.kind, d.tx_base};
+  hipLaunchKernelGGL(k_byron_witness_emit, dim3(wit::lane_grid(n)), dim3(kBlock), 0, st, raw, off,
+                     len, n, magic_cfg, d.ntx, d.nwit, d.tx_begin, d.wit_begin, (uint64_t)d.tx_cap,
+                     (uint64_t)d.wit_cap, rows, d.magic, status);
   return launch_check();
 }
 
-int launch_byron_witness_verify(hipStream_t st, size_t wit_cap, const uint64_t* rows,
-                                const uint8_t* vk, const uint8_t* sig, const uint32_t* wit_tx,
-                                const uint8_t* tx_id, size_t tx_cap, uint64_t tx_base,
-                                const uint64_t* wit_begin, size_t n, const uint64_t* magic,
-                                uint8_t* kind, uint8_t* wit_ok) {
-  if (wit_cap == 0 || n == 0) return OURO_OK;
+int launch_byron_witness_verify(hipStream_t st, size_t n, const WitnessDev& d) {
+  if (d.wit_cap == 0 || n == 0) return OURO_OK;
   DeviceState* ds;
   int rc = device_state(&ds);
   if (rc) return rc;
   int grid;
   int32_t* scr;
-  if ((rc = plan(ds, kEd, wit_cap, st, &grid, &scr))) return rc;
-  hipLaunchKernelGGL(k_byron_witness_verify, dim3(grid), dim3(kBlock), 0, st, rows, vk, sig, wit_tx,
-                     tx_id, (uint64_t)tx_cap, tx_base, wit_begin, n, magic, kind, wit_ok, scr,
-                     ds->btab);
-  hipLaunchKernelGGL(k_byron_witness_tail, dim3(lane_grid(wit_cap)), dim3(kBlock), 0, st, rows,
-                     wit_cap, kind, wit_ok);
+  if ((rc = plan(ds, kEd, d.wit_cap, st, &grid, &scr))) return rc;
+  hipLaunchKernelGGL(k_byron_witness_verify, dim3(grid), dim3(kBlock), 0, st, d.rows, d.vk, d.sig,
+                     d.wit_tx, d.tx_id, (uint64_t)d.tx_cap, d.tx_base, d.wit_begin, n, d.magic,
+                     d.kind, d.wit_ok, scr, ds->btab);
+  wit::launch_tail(st, d);
   return launch_check();
 }
 
 int launch_byron_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
-                                const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
-                                uint8_t* verdict, uint32_t* n_bad) {
-  if (n == 0) return OURO_OK;
-  hipLaunchKernelGGL(k_byron_witness_finish, dim3(lane_grid(n)), dim3(kBlock), 0, st, n, status,
-                     wit_begin, wit_ok, (uint64_t)wit_cap, verdict, n_bad);
-  return launch_check();
+                                const WitnessDev& d, uint8_t* verdict, uint32_t* n_bad) {
+  return wit::launch_finish<ByronWit>(st, n, status, d, verdict, n_bad);
 }
 
 }  // namespace ouro_rt

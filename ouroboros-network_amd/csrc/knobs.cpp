@@ -48,13 +48,13 @@ void load(Knobs& k) {
   read_int(k.cbor_ramp, "OURO_CBOR_RAMP", 0);
   read_int(k.block_sort, "OURO_BLOCK_SORT", 1);
   // the raw bytes one group of whole blocks of ouro_block_witness_verify_cbor
-  // uploads and verifies at a time (witness_api.cpp; a block larger than the
+  // uploads and verifies at a time (witness_flow.h; a block larger than the
   // budget is a group of its own); the tests force it small so that a batch
   // spans several groups
   read_size<size_t>(k.witness_group_bytes, "OURO_WITNESS_GROUP_BYTES", 0);
   // the same budget for ouro_byron_block_integrity_verify_cbor (byron_block_api.cpp)
   read_size<size_t>(k.byron_block_group_bytes, "OURO_BYRON_BLOCK_GROUP_BYTES", 0);
-  // ... and for ouro_byron_block_witness_verify_cbor (byron_witness_api.cpp)
+  // ... and for ouro_byron_block_witness_verify_cbor (witness_flow.h too)
   read_size<size_t>(k.byron_witness_group_bytes, "OURO_BYRON_WITNESS_GROUP_BYTES", 0);
   read_int(k.lat_block, "OURO_LAT_BLOCK", 0);
   read_int(k.lat_quad, "OURO_LAT_QUAD", 1);

@@ -136,38 +136,72 @@ void launch_plan_stage(hipStream_t st, unsigned blocks, const uint4* src, uint4*
 void launch_plan_stage_ranges(hipStream_t st, unsigned blocks, const uint4* src, uint4* dst,
                               const PlanRanges& r, uint64_t* stamp);
 
-// the transaction-witness kernels (kernels_witness.hip; cbor_witness.h), each
-// checking its own launches.  Every pointer is device memory.
-// count: status, ntx and nwit per block (zeros where it does not slice)
+// ---- the two-level exclusive scan (scan_excl.h), as the host units size it ----
+// a tile is kScanTile consecutive items; the work of a scan of `vals` count
+// arrays over n items: vals * scan_tiles(n) words of tile sums, then
+// scan_rows_words(vals) words: rows[q] = min(total, capacity), rows[vals + q] =
+// the total
+constexpr size_t kScanTile = 1024;
+inline size_t scan_tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; }
+constexpr size_t scan_rows_words(int vals) { return 2 * (size_t)vals; }
+
+// ---- the transaction-witness kernels, Shelley (kernels_witness.hip;
+// cbor_witness.h) and Byron (kernels_byron_witness.hip; cbor_byron_witness.h),
+// each checking its own launches.  Every pointer is device memory.  One
+// sequence over n blocks (witness_flow.h lays it out): ----
+constexpr int kWitnessVals = 2;  // the scanned count arrays: ntx, nwit
+struct WitnessDev {
+  uint32_t *ntx, *nwit;   // n each: the count pass
+  uint64_t *sums, *rows;  // kWitnessVals * scan_tiles(n); scan_rows_words(kWitnessVals)
+  uint64_t* magic;        // n: the magic block i's messages use (Byron; null for Shelley)
+  // tx_cap spans for launch_blake2b; vk (wit_cap x 32, Byron x 64: a redeem key
+  // then 32 zero bytes) and sig (wit_cap x 64), 16-byte aligned; b2b:
+  // launch_blake2b's work (tx_cap items)
+  uint64_t* tx_off;
+  uint32_t* tx_len;
+  uint8_t *vk, *sig;
+  void* b2b;
+  // the call's rows (ouro_block_witness_out): block i owns the rows from
+  // tx_begin[i] / wit_begin[i] (n + 1 each, [n] = the totals) as far as the
+  // capacities hold them; wit_tx = tx_base + the transaction's row of tx_id
+  size_t tx_cap, wit_cap;
+  uint64_t *tx_begin, *wit_begin;
+  uint64_t tx_base;
+  uint8_t* tx_id;
+  uint32_t* wit_tx;
+  uint8_t *kind, *wit_ok;
+};
+// count: status, ntx and nwit per block (zeros unless the status is OURO_PACK_OK)
+// scan: both count arrays into tx_begin / wit_begin, cut at tx_cap / wit_cap;
+//   rows[1] = min(total, wit_cap) is the row count the later kernels read
+// emit: every row to "not written", then the emit pass of the blocks that fit
+//   (status OURO_PACK_ECAP for a sliced one that does not); magic_cfg: the
+//   configured magic, or -1: each header's own field (Byron; Shelley ignores it)
+// verify: per witness row, Ed25519 over its transaction id / ByronDSIGN under
+//   vk[0:32] over tag || CBOR(magic) || 58 20 || tx id, the message built in
+//   the lane; rows nothing was emitted to and rows past the count get zeros
+// finish: n_bad[i] and verdict[i] = OURO_WIT_ALL_OK / OURO_BYW_ALL_OK (Byron:
+//   for an EBB too)
+// The two families have one shape, so that witness_flow.h names either.
 int launch_witness_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes, const uint64_t* off,
                          const uint32_t* len, size_t n, uint8_t* status, uint32_t* ntx,
                          uint32_t* nwit);
-// the exclusive scan of both count arrays into tx_begin / wit_begin (n + 1
-// each, [n] = the totals); sums: 2 * witness_scan_tiles(n) words of work;
-// rows[0..1] = min(total, capacity), what the later kernels read
-size_t witness_scan_tiles(size_t n);
-int launch_witness_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* nwit,
-                        uint64_t* sums, uint64_t* tx_begin, uint64_t* wit_begin, size_t tx_cap,
-                        size_t wit_cap, uint64_t* rows);
-// every row to "not written", then the emit pass of the blocks that fit
-// (status OURO_PACK_ECAP for a sliced one that does not).  tx_off / tx_len:
-// tx_cap spans for launch_blake2b; vk / sig (16-byte aligned), wit_tx, kind:
-// wit_cap rows; wit_tx = tx_base + the transaction's row
+int launch_witness_scan(hipStream_t st, size_t n, const WitnessDev& d);
 int launch_witness_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off, const uint32_t* len,
-                        size_t n, const uint32_t* ntx, const uint32_t* nwit,
-                        const uint64_t* tx_begin, const uint64_t* wit_begin, size_t tx_cap,
-                        size_t wit_cap, uint64_t tx_base, uint64_t* tx_off, uint32_t* tx_len,
-                        uint8_t* vk, uint8_t* sig, uint32_t* wit_tx, uint8_t* kind,
-                        uint8_t* status);
-// Ed25519 per witness row over its transaction id (tx_id: tx_cap x 32, row
-// wit_tx - tx_base); the row count is read from rows[1] on the device; rows nothing was emitted to
-// and rows past the count get zeros
-int launch_witness_verify(hipStream_t st, size_t wit_cap, const uint64_t* rows, const uint8_t* vk,
-                          const uint8_t* sig, const uint32_t* wit_tx, const uint8_t* tx_id,
-                          size_t tx_cap, uint64_t tx_base, uint8_t* kind, uint8_t* wit_ok);
-int launch_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
-                          const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
+                        size_t n, int64_t magic_cfg, const WitnessDev& d, uint8_t* status);
+int launch_witness_verify(hipStream_t st, size_t n, const WitnessDev& d);
+int launch_witness_finish(hipStream_t st, size_t n, const uint8_t* status, const WitnessDev& d,
                           uint8_t* verdict, uint32_t* n_bad);
+int launch_byron_witness_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes,
+                               const uint64_t* off, const uint32_t* len, size_t n, uint8_t* status,
+                               uint32_t* ntx, uint32_t* nwit);
+int launch_byron_witness_scan(hipStream_t st, size_t n, const WitnessDev& d);
+int launch_byron_witness_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off,
+                              const uint32_t* len, size_t n, int64_t magic_cfg, const WitnessDev& d,
+                              uint8_t* status);
+int launch_byron_witness_verify(hipStream_t st, size_t n, const WitnessDev& d);
+int launch_byron_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
+                                const WitnessDev& d, uint8_t* verdict, uint32_t* n_bad);
 
 // the Byron whole-block integrity kernels (kernels_byron_block.hip;
 // cbor_byron_block.h), each checking its own launches.  Every pointer is device
@@ -175,7 +209,7 @@ int launch_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
 // them out; each array 64-byte aligned):
 struct ByronBlockDev {
   uint32_t *ntx, *gather_n, *msg_n;  // n each: the count pass
-  uint64_t *sums, *rows;             // 3 * byron_block_scan_tiles(n); 6: capped totals, totals
+  uint64_t *sums, *rows;             // 3 * scan_tiles(n); 6: capped totals, totals
   // n + 1 each ([n] = the totals); msg_off is the third.  msg_off is a scan only
   // until the emit pass: emit leaves a block's own begin where it wrote a
   // message and puts 0 where it wrote none (an EBB, a block that does not
@@ -211,7 +245,6 @@ int launch_byron_block_count(hipStream_t st, const uint8_t* raw, size_t raw_byte
                              uint8_t* status, uint32_t* ntx, uint32_t* gather, uint32_t* msg);
 // the exclusive scan of the three count arrays (n + 1 each, [n] = the totals);
 // rows[q] = min(total, capacity), rows[3 + q] = total
-size_t byron_block_scan_tiles(size_t n);
 int launch_byron_block_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* gather,
                             const uint32_t* msg, uint64_t* sums, uint64_t* tx_begin,
                             uint64_t* g_begin, uint64_t* msg_begin, size_t tx_cap,
@@ -237,40 +270,6 @@ int launch_byron_block_finish(hipStream_t st, size_t n, int64_t magic, const uin
                               const uint64_t* hdr_magic, const uint8_t* claimed,
                               const uint8_t* root, const uint8_t* wit, const uint8_t* seg,
                               const uint8_t* sig_ok, uint8_t* verdict, uint8_t* tx_root);
-
-// the Byron transaction-witness kernels (kernels_byron_witness.hip;
-// cbor_byron_witness.h), each checking its own launches.  Every pointer is
-// device memory.  They follow the launch_witness_* ones above; what differs:
-// count: status, ntx and nwit per block (zeros unless the status is OURO_PACK_OK)
-int launch_byron_witness_count(hipStream_t st, const uint8_t* raw, size_t raw_bytes,
-                               const uint64_t* off, const uint32_t* len, size_t n, uint8_t* status,
-                               uint32_t* ntx, uint32_t* nwit);
-// sums: 2 * byron_witness_scan_tiles(n) words of work; rows[0..1] =
-// min(total, capacity), rows[2..3] = the totals
-size_t byron_witness_scan_tiles(size_t n);
-int launch_byron_witness_scan(hipStream_t st, size_t n, const uint32_t* ntx, const uint32_t* nwit,
-                              uint64_t* sums, uint64_t* tx_begin, uint64_t* wit_begin,
-                              size_t tx_cap, size_t wit_cap, uint64_t* rows);
-// vk and sig: wit_cap x 64 each (a redeem key then 32 zero bytes); magic: n,
-// the magic block i's messages use (magic_cfg, or -1: its header's own field)
-int launch_byron_witness_emit(hipStream_t st, const uint8_t* raw, const uint64_t* off,
-                              const uint32_t* len, size_t n, int64_t magic_cfg, const uint32_t* ntx,
-                              const uint32_t* nwit, const uint64_t* tx_begin,
-                              const uint64_t* wit_begin, size_t tx_cap, size_t wit_cap,
-                              uint64_t tx_base, uint64_t* tx_off, uint32_t* tx_len, uint8_t* vk,
-                              uint8_t* sig, uint32_t* wit_tx, uint8_t* kind, uint64_t* magic,
-                              uint8_t* status);
-// ByronDSIGN per witness row under vk[0:32] over tag || CBOR(magic) || 58 20 ||
-// tx id, the message built in the lane (wit_begin, n, magic: the row's block)
-int launch_byron_witness_verify(hipStream_t st, size_t wit_cap, const uint64_t* rows,
-                                const uint8_t* vk, const uint8_t* sig, const uint32_t* wit_tx,
-                                const uint8_t* tx_id, size_t tx_cap, uint64_t tx_base,
-                                const uint64_t* wit_begin, size_t n, const uint64_t* magic,
-                                uint8_t* kind, uint8_t* wit_ok);
-// verdict[i] = OURO_BYW_ALL_OK for an EBB too
-int launch_byron_witness_finish(hipStream_t st, size_t n, const uint8_t* status,
-                                const uint64_t* wit_begin, const uint8_t* wit_ok, size_t wit_cap,
-                                uint8_t* verdict, uint32_t* n_bad);
 
 // the forging-side kernels (kernels_forge.hip; forge.h), each checking its own
 // launch, on k_ed25519_verify's launch shape and scratch slots.  Every pointer

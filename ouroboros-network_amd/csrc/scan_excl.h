@@ -1,8 +1,9 @@
 // scan_excl.h -- the two-level exclusive scan of kVals count arrays over n
-// items, written once as a template (kernels_byron_witness.hip instantiates it
-// with two values; kernels_witness.hip and kernels_byron_block.hip still carry
-// their own copies).  Device code of the unit that includes it;
-// needs launch.h's kBlock.
+// items, written once as a template: kernels_witness.hip and
+// kernels_byron_witness.hip instantiate it with two values,
+// kernels_byron_block.hip with three.  Device code of the unit that includes
+// it, inside that unit's renamed namespace; needs launch.h's kBlock.  The host
+// units size its work from launches.h (kScanTile, scan_tiles, scan_rows_words).
 //
 // A tile is kScanTile consecutive items: kScanPer per thread of one workgroup.
 // Level 1 (k_scan_tile_sums) reduces every tile, level 2 (k_scan_sums, ONE
@@ -16,13 +17,14 @@
 
 #include "common.h"
 #include "launch.h"
+#include "launches.h"
 
 namespace ouro {
 namespace scan {
 
 constexpr int kScanPer = 4;
 constexpr int kScanTile = kBlock * kScanPer;
-inline size_t tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; }
+static_assert(kScanTile == ouro_rt::kScanTile, "launches.h sizes the tile sums by its own kScanTile");
 
 // cnt[q]: n counts; begin[q]: n + 1 (begin[q][n] = the total); cap[q]: the
 // capacity rows[q] = min(total, cap[q]) is cut at, rows[kVals + q] = the total
@@ -153,10 +155,11 @@ __global__ void __launch_bounds__(kBlock) k_scan_apply(size_t n, Args<kVals> a,
   }
 }
 
-// the three launches on `st` (n > 0); sums: kVals * tiles(n) words, rows: 2 kVals
+// the three launches on `st` (n > 0); sums: kVals * scan_tiles(n) words, rows:
+// scan_rows_words(kVals)
 template <int kVals>
 inline void launch(hipStream_t st, size_t n, const Args<kVals>& a, uint64_t* sums, uint64_t* rows) {
-  const unsigned nt = (unsigned)std::min<size_t>(tiles(n), 4096);
+  const unsigned nt = (unsigned)std::min<size_t>(ouro_rt::scan_tiles(n), 4096);
   hipLaunchKernelGGL(k_scan_tile_sums<kVals>, dim3(nt), dim3(kBlock), 0, st, n, a, sums);
   hipLaunchKernelGGL(k_scan_sums<kVals>, dim3(1), dim3(kBlock), 0, st, n, a, sums, rows);
   hipLaunchKernelGGL(k_scan_apply<kVals>, dim3(nt), dim3(kBlock), 0, st, n, a, sums);

@@ -115,3 +115,27 @@ def test_every_einval():
     # the work area of the device form grows with each of its arguments
     wb = _native.load().ouro_block_witness_work_bytes
     assert wb(10, 5, 7) < wb(11000, 5, 7) and wb(10, 5, 7) < wb(10, 500, 7) < wb(10, 500, 700)
+
+
+# ouro_block_witness_work_bytes(n, tx_cap, wit_cap) as the entry answered before
+# the witness flow was shared between the eras: n at one tile of the scan, one
+# past it and many; no rows, one row, and capacities at which every term counts
+WORK_BYTES = {
+    (1, 0, 0): 640,
+    (1, 1, 1): 960,
+    (1, 100003, 250007): 25601536,
+    (1024, 0, 0): 8704,
+    (1024, 1, 1): 9024,
+    (1024, 100003, 250007): 25609600,
+    (1025, 0, 0): 8832,
+    (1025, 1, 1): 9152,
+    (1025, 100003, 250007): 25609728,
+    (70000, 0, 0): 561600,
+    (70000, 1, 1): 561920,
+    (70000, 100003, 250007): 26162496,
+}
+
+
+def test_work_area_sizes_are_unchanged():
+    wb = _native.load().ouro_block_witness_work_bytes
+    assert {a: int(wb(*a)) for a in WORK_BYTES} == WORK_BYTES

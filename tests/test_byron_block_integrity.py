@@ -137,6 +137,31 @@ def test_count_einval(entry):
     assert call(n=0) == _native.OURO_OK and tot.tolist() == [0, 0, 0]
 
 
+# ouro_byron_block_work_bytes(n, tx_cap, gather_cap, msg_cap) as the entry
+# answered before its scan became scan_excl.h's: n at one tile of the scan, one
+# past it and many; no rows, one of each, and capacities at which every term
+# counts
+WORK_BYTES = {
+    (1, 0, 0, 0): 2176,
+    (1, 1, 1, 1): 2496,
+    (1, 100003, 250007, 3000017): 7652544,
+    (1024, 0, 0, 0): 591680,
+    (1024, 1, 1, 1): 592000,
+    (1024, 100003, 250007, 3000017): 8242048,
+    (1025, 0, 0, 0): 593024,
+    (1025, 1, 1, 1): 593344,
+    (1025, 100003, 250007, 3000017): 8243392,
+    (70000, 0, 0, 0): 40392448,
+    (70000, 1, 1, 1): 40392768,
+    (70000, 100003, 250007, 3000017): 48042816,
+}
+
+
+def test_work_area_sizes_are_unchanged():
+    wb = _native.load().ouro_byron_block_work_bytes
+    assert {a: int(wb(*a)) for a in WORK_BYTES} == WORK_BYTES
+
+
 def test_device_entry_einval_before_any_work():
     lib = _native.load()
     a = _args()

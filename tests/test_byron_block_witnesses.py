@@ -163,6 +163,31 @@ def test_every_einval(suffix):
     assert _call(verify, wit_cap=1 << 32) == _native.OURO_EINVAL
 
 
+# ouro_byron_block_witness_work_bytes(n, tx_cap, wit_cap) as the entry answered
+# before the witness flow was shared between the eras: n at one tile of the
+# scan, one past it and many; no rows, one row, and capacities at which every
+# term counts
+WORK_BYTES = {
+    (1, 0, 0): 704,
+    (1, 1, 1): 1024,
+    (1, 100003, 250007): 33601792,
+    (1024, 0, 0): 16896,
+    (1024, 1, 1): 17216,
+    (1024, 100003, 250007): 33617984,
+    (1025, 0, 0): 17088,
+    (1025, 1, 1): 17408,
+    (1025, 100003, 250007): 33618176,
+    (70000, 0, 0): 1121600,
+    (70000, 1, 1): 1121920,
+    (70000, 100003, 250007): 34722688,
+}
+
+
+def test_work_area_sizes_are_unchanged():
+    wb = _native.load().ouro_byron_block_witness_work_bytes
+    assert {a: int(wb(*a)) for a in WORK_BYTES} == WORK_BYTES
+
+
 def test_device_entry_einval_before_any_work():
     name = VERIFY + "_device"
     wb = _native.load().ouro_byron_block_witness_work_bytes

@@ -19,7 +19,7 @@ from ouroboros_network_amd import witness as W
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCAN_TILE = 1024     # csrc/kernels_witness.hip kScanTile: one workgroup's tile of the scan
+SCAN_TILE = 1024     # csrc/scan_excl.h kScanTile: one workgroup's tile of the scan
 
 
 @pytest.fixture(scope="module")
@@ -62,7 +62,8 @@ def test_one_call_entry_on_the_case_set(gpu_lib, cs):
     assert not ((r.verdict != 0) & (r.status != B.PACK_OK)).any()
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, SCAN_TILE + 7])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 7,
+                               2 * SCAN_TILE])
 def test_block_counts_across_the_scan_boundaries(gpu_lib, pool, n):
     raws = [pool[(5 * i + i // 7) % len(pool)] for i in range(n)]
     want = WC.expected_arrays(raws)

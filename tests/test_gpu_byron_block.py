@@ -19,7 +19,7 @@ from ouroboros_network_amd import byron_block as BB
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCAN_TILE = 1024     # csrc/kernels_byron_block.hip kScanTile: one workgroup's tile of the scan
+SCAN_TILE = 1024     # csrc/scan_excl.h kScanTile: one workgroup's tile of the scan
 
 
 @pytest.fixture(scope="module")
